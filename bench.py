@@ -227,6 +227,57 @@ def cpu_baseline_big(config, T, Mb, deg, nstates, E_per_sweep):
                        f"(flops.node_update_flops over the config's degrees, T = {T}) -> {s_per_sweep:.0f} s per sweep")}
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most 64 MB in all
+DUMP_EDGE_SAMPLE = 64          # messages sampled for --dump-outputs (fixed seed)
+
+
+def _message_marginals(cores):
+    """[T+1, q, q] per-time marginals of one message (MPEM2 cores [b_t, b_{t+1}, q, q]): the function the message
+    represents, summed over every other time step.  Gauge free, unlike the cores, so two builds compare entry by entry."""
+    S = [a.sum(axis=(2, 3)) for a in cores]
+    left = [np.ones(1)]
+    for s in S[:-1]:
+        v = left[-1] @ s
+        left.append(v / np.abs(v).max())
+    right = [np.ones(1)]
+    for s in S[:0:-1]:
+        v = s @ right[-1]
+        right.append(v / np.abs(v).max())
+    right = right[::-1]
+    out = np.empty((len(cores),) + cores[0].shape[2:])
+    for t, a in enumerate(cores):
+        m = np.einsum("a,abxy,b->xy", left[t], a, right[t])
+        out[t] = m / m.sum()
+    return out
+
+
+def dump_outputs(path, bp, parts):
+    """--dump-outputs: what the timed path computed in its last step, as float64 .npy files under `path` - beliefs and
+    free-energy terms of the nodes the step updated (`parts`: (lo, hi, beliefs, f) per node block), the bond table of
+    every edge, and the per-time marginals of a seeded sample of the messages the step wrote (their edge ids beside)."""
+    os.makedirs(path, exist_ok=True)
+    ptr, _, oute = bp.g.nbr_arrays()
+    written = np.unique(np.concatenate([np.asarray(oute[int(ptr[lo]):int(ptr[hi])]) for lo, hi, _, _ in parts]))
+    rng = np.random.default_rng(0)
+    edges = np.sort(rng.choice(written, size=min(DUMP_EDGE_SAMPLE, written.size), replace=False))
+    marg = []
+    for k in range(0, edges.size, 16):                 # a few messages per download: bounded host memory
+        chunk = edges[k:k + 16]
+        msgs = bp.get_messages(edges=chunk)
+        marg += [_message_marginals(msgs[int(e)]) for e in chunk]
+    out = {"beliefs": np.concatenate([p_[2] for p_ in parts]),
+           "free_energy": np.concatenate([p_[3] for p_ in parts]),
+           "bonds": bp.bonds(),
+           "message_marginals": np.stack(marg),
+           "message_edges": edges}
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,8 +299,15 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (gloo = rehearsal on one GPU)")
     ap.add_argument("--dump-beliefs", default="", help="write rank-0 beliefs + f to this .npy file (parity checks)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed as float64 .npy files under DIR "
+                         "(beliefs, free-energy terms, bond table, per-time marginals of a seeded sample of messages)")
     ap.add_argument("--phase-profile", action="store_true", help="print the engine phase profile to stderr")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     import torch
     import torch.distributed as dist
@@ -404,7 +462,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    if args.dump_beliefs:
+    if args.dump_beliefs or args.dump_outputs:
         # beliefs / f of the nodes this rank owns; rank 0 gathers them
         b = np.array(M.beliefs(bp))[lo:hi]
         f = np.zeros(N)
@@ -414,9 +472,11 @@ def main():
             dist.all_gather_object(parts, (lo, hi, b, f[lo:hi]))
         else:
             parts = [(lo, hi, b, f[lo:hi])]
-        if rank == 0:
+        if rank == 0 and args.dump_beliefs:
             ball = np.concatenate([p_[2] for p_ in parts]); fall = np.concatenate([p_[3] for p_ in parts])
             np.save(args.dump_beliefs, {"beliefs": ball, "f": fall}, allow_pickle=True)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, bp, parts)
     if rank == 0 and args.phase_profile:
         bp._L.mpbp_phase_profile(bp._h, ph.ctypes.data_as(C.POINTER(C.c_double)), 24, 0)
         names = ["stage", "Y1", "Y2", "qr1_panel", "qr1_trail", "Lf", "N", "Mt", "qr2_panel", "qr2_trail", "jacobi",
