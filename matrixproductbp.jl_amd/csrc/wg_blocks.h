@@ -794,6 +794,88 @@ __device__ __forceinline__ void qr_gramN(const gdbl* Y, long ld, int rows32, int
   }
 }
 
+// NPR products of NP 16-column panels in ONE pass over the rows from `jrow` (a multiple of 16), every panel read once:
+// G_k[i + 16 j] = sum_r X_a[r][i] X_b[r][j],  (a, b) = (pa[k], pb[k]).  Panel p starts at column jc[p]; if hd[p] it is a
+// full reflector panel stored in place (unit lower-trapezoidal head at row jc[p], zero above), else a plain column tile.
+// This is how the Gram pass of a panel also forms the V^T C of the in-block tile update that follows it (the first pass
+// of qr_tile_update_all, which then skips it, and all of the V^T C of qr_tile_update2_all): the reflector panels are
+// streamed once, not twice.
+// Results in big[256 k ...]; partials are reduced four products at a time through WG_WAVES * 1024 doubles of `big`.
+template <int NP, int NPR>
+__device__ __forceinline__ void qr_gram_multi(const gdbl* Y, long ld, int rows32, int jrow, const int (&jc)[NP],
+                                              const bool (&hd)[NP], const int (&pa)[NPR], const int (&pb)[NPR], ldbl* big) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4, l15 = lane & 15;
+  const int nrb = (rows32 - jrow) >> 4;
+  const gdbl* col[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) col[p] = Y + (long)(jc[p] + l15) * ld + jrow + 4 * g;
+  d4 acc[NPR];
+#pragma unroll
+  for (int k = 0; k < NPR; k++) acc[k] = d4{0, 0, 0, 0};
+  auto mask = [&](d4& v, int rb, int p) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      const int rr = jrow + 16 * rb + 4 * g + e - jc[p];      // relative to the panel's diagonal block
+      double a = v[e];
+      if (hd[p]) a = (rr < 16) ? ((rr > l15) ? a : ((rr == l15) ? 1.0 : 0.0)) : a;
+      v[e] = (rb < nrb) ? a : 0.0;
+    }
+  };
+  d4 x[2][NP];
+  auto load = [&](int rb, d4 (&b)[NP]) {
+    const int rbc = min(rb, nrb - 1);
+#pragma unroll
+    for (int p = 0; p < NP; p++) b[p] = *reinterpret_cast<const gd4*>(col[p] + 16 * rbc);
+  };
+  auto comp = [&](int rb, d4 (&b)[NP]) {
+#pragma unroll
+    for (int p = 0; p < NP; p++) mask(b[p], rb, p);
+#pragma unroll
+    for (int k = 0; k < NPR; k++)
+#pragma unroll
+      for (int e = 0; e < 4; e++) acc[k] = mfma(b[pa[k]][e], b[pb[k]][e], acc[k]);
+  };
+  if (wave < nrb) load(wave, x[0]);
+  for (int rb = wave; rb < nrb; rb += 2 * WG_WAVES) {
+    load(rb + WG_WAVES, x[1]);
+    comp(rb, x[0]);
+    load(rb + 2 * WG_WAVES, x[0]);
+    comp(rb + WG_WAVES, x[1]);
+  }
+  constexpr int NR = (NPR + 3) / 4;                             // reduction rounds of up to four products
+  constexpr int PER = (1024 + WG_THREADS - 1) / WG_THREADS;
+  double s1[NR][PER];
+#pragma unroll
+  for (int rd = 0; rd < NR; rd++) {
+    const int nk = min(4, NPR - 4 * rd);
+    if (rd > 0) __syncthreads();
+#pragma unroll
+    for (int k = 4 * rd; k < min(4 * rd + 4, NPR); k++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) big[wave * 1024 + 256 * (k - 4 * rd) + (g + 4 * r) + 16 * l15] = acc[k][r];
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+      const int idx = tid + e * WG_THREADS;
+      s1[rd][e] = 0.0;
+      if (idx < 256 * nk) {
+#pragma unroll
+        for (int w = 0; w < WG_WAVES; w++) s1[rd][e] += big[w * 1024 + idx];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int rd = 0; rd < NR; rd++)
+#pragma unroll
+    for (int e = 0; e < PER; e++) {
+      const int idx = tid + e * WG_THREADS;
+      if (idx < 256 * min(4, NPR - 4 * rd)) big[1024 * rd + idx] = s1[rd][e];
+    }
+  __syncthreads();
+}
+
 // T of the block reflector (dlarft) from the Gram matrix G = V^T V in `big`: row i of T depends only on its own
 // earlier entries, so lane i builds row i in registers with no synchronisation:
 //   T(i,j) = -tau_j sum_{i2=i}^{j-1} T(i,i2) G(i2,j)  (i < j),  T(j,j) = tau_j.
@@ -1096,16 +1178,17 @@ __device__ __forceinline__ void qr_trail2(gdbl* Y, long ld, int rows32, int j0, 
 }
 
 // Update ONE 16-column tile (first column cb0) by panel (j0, nb) with all waves working on different rows:
-// W0 partials -> LDS, every wave then applies W = T^T W0 to its own 32-row stages.
+// W0 partials -> LDS, every wave then applies W = T^T W0 to its own 32-row stages.  W0f != nullptr: W0 = V^T C is already
+// in LDS (W0f[i + 16 j], from the Gram pass of the panel, qr_gram_multi) and the first pass over the rows is skipped.
 __device__ __forceinline__ void qr_tile_update_all(gdbl* Y, long ld, int rows32, int j0, int nb, int cb0,
-                                                   const ldbl* Ts, ldbl* big) {
+                                                   const ldbl* Ts, ldbl* big, const ldbl* W0f = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l15 = lane & 15;
   const int nrb = (rows32 - j0) >> 4;
   const gdbl* vcol = Y + (long)(j0 + l15) * ld + j0 + 4 * g;
   const gdbl* ccol = Y + (long)(cb0 + l15) * ld + j0 + 4 * g;
   d4 acc = d4{0, 0, 0, 0};
-  for (int rb = wave; rb < nrb; rb += WG_WAVES) {
+  for (int rb = W0f ? nrb : wave; rb < nrb; rb += WG_WAVES) {
     d4 v = *reinterpret_cast<const gd4*>(vcol + 16 * rb);
     d4 c = *reinterpret_cast<const gd4*>(ccol + 16 * rb);
 #pragma unroll
@@ -1118,15 +1201,20 @@ __device__ __forceinline__ void qr_tile_update_all(gdbl* Y, long ld, int rows32,
 #pragma unroll
     for (int e = 0; e < 4; e++) acc = mfma(v[e], c[e], acc);
   }
-#pragma unroll
-  for (int r = 0; r < 4; r++) big[wave * 256 + (g + 4 * r) + 16 * l15] = acc[r];
-  __syncthreads();
-  // every wave sums the partials into its own W0 registers (C layout: row g+4r, col l15)
   d4 w0 = d4{0, 0, 0, 0};
+  if (W0f) {
 #pragma unroll
-  for (int w = 0; w < WG_WAVES; w++)
+    for (int r = 0; r < 4; r++) w0[r] = W0f[(g + 4 * r) + 16 * l15];
+  } else {
 #pragma unroll
-    for (int r = 0; r < 4; r++) w0[r] += big[w * 256 + (g + 4 * r) + 16 * l15];
+    for (int r = 0; r < 4; r++) big[wave * 256 + (g + 4 * r) + 16 * l15] = acc[r];
+    __syncthreads();
+    // every wave sums the partials into its own W0 registers (C layout: row g+4r, col l15)
+#pragma unroll
+    for (int w = 0; w < WG_WAVES; w++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) w0[r] += big[w * 256 + (g + 4 * r) + 16 * l15];
+  }
   d4 wv = d4{0, 0, 0, 0};
 #pragma unroll
   for (int s = 0; s < 4; s++) wv = mfma(Ts[(4 * s + g) + 16 * l15], w0[s], wv);
@@ -1165,60 +1253,24 @@ __device__ __forceinline__ void qr_tile_update_all(gdbl* Y, long ld, int rows32,
 }
 
 // Update NT adjacent 16-column tiles (first column cb0) by the panel PAIR a (j0), b (j0+16) with all waves working
-// on different rows (the row-parallel counterpart of qr_trail2): partial Va^T C, Vb^T C -> LDS, then every wave
-// forms Wa, Wb and applies them to its own 32-row stages.  The V fragments are loaded once for all NT tiles.
-// `big`: WG_WAVES * 512 * NT doubles.
+// on different rows (the row-parallel counterpart of qr_trail2): Va^T C and Vb^T C of tile q are already in LDS at
+// W0 + 512 q and W0 + 512 q + 256 (formed by the Gram pass of panel b, qr_gram_multi); every wave forms Wa, Wb and applies
+// them to its own 32-row stages.  The V fragments are loaded once for all NT tiles.
 template <int NT>
 __device__ __forceinline__ void qr_tile_update2_all(gdbl* Y, long ld, int rows32, int j0, int cb0, const ldbl* TsA,
-                                                    const ldbl* TsB, const ldbl* Sm, ldbl* big) {
+                                                    const ldbl* TsB, const ldbl* Sm, const ldbl* W0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, l15 = lane & 15;
-  const int nrb = (rows32 - j0) >> 4;
-  const gdbl* vacol = Y + (long)(j0 + l15) * ld + j0 + 4 * g;
-  const gdbl* vbcol = Y + (long)(j0 + 16 + l15) * ld + j0 + 4 * g;
-  d4 acca[NT], accb[NT];
-#pragma unroll
-  for (int q = 0; q < NT; q++) { acca[q] = d4{0, 0, 0, 0}; accb[q] = d4{0, 0, 0, 0}; }
-  for (int rb = wave; rb < nrb; rb += WG_WAVES) {
-    d4 va = *reinterpret_cast<const gd4*>(vacol + 16 * rb);
-    d4 vb = *reinterpret_cast<const gd4*>(vbcol + 16 * rb);
-    d4 c[NT];
-#pragma unroll
-    for (int q = 0; q < NT; q++) c[q] = *reinterpret_cast<const gd4*>(Y + (long)(cb0 + 16 * q + l15) * ld + j0 + 4 * g + 16 * rb);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      const int rho = 4 * g + e;
-      double a = va[e], b = vb[e];
-      a = (rb == 0) ? ((rho > l15) ? a : ((rho == l15) ? 1.0 : 0.0)) : a;
-      b = (rb == 1) ? ((rho > l15) ? b : ((rho == l15) ? 1.0 : 0.0)) : b;
-      va[e] = a;
-      vb[e] = (rb >= 1) ? b : 0.0;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; e++)
-#pragma unroll
-      for (int q = 0; q < NT; q++) { acca[q] = mfma(va[e], c[q][e], acca[q]); accb[q] = mfma(vb[e], c[q][e], accb[q]); }
-  }
-  constexpr int NVAL = 512 * NT;
-#pragma unroll
-  for (int q = 0; q < NT; q++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      big[wave * NVAL + 512 * q + (g + 4 * r) + 16 * l15] = acca[q][r];
-      big[wave * NVAL + 512 * q + 256 + (g + 4 * r) + 16 * l15] = accb[q][r];
-    }
-  __syncthreads();
+  (void)tid;
   d4 wa[NT], wb[NT];
 #pragma unroll
   for (int q = 0; q < NT; q++) {
-    d4 wa0 = d4{0, 0, 0, 0}, wb0 = d4{0, 0, 0, 0};
+    d4 wa0, wb0;
 #pragma unroll
-    for (int w = 0; w < WG_WAVES; w++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        wa0[r] += big[w * NVAL + 512 * q + (g + 4 * r) + 16 * l15];
-        wb0[r] += big[w * NVAL + 512 * q + 256 + (g + 4 * r) + 16 * l15];
-      }
+    for (int r = 0; r < 4; r++) {
+      wa0[r] = W0[512 * q + (g + 4 * r) + 16 * l15];
+      wb0[r] = W0[512 * q + 256 + (g + 4 * r) + 16 * l15];
+    }
     wa[q] = d4{0, 0, 0, 0}; wb[q] = d4{0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < 4; s++) wa[q] = mfma(TsA[(4 * s + g) + 16 * l15], wa0[s], wa[q]);
@@ -1747,17 +1799,28 @@ __device__ __attribute__((noinline)) void qr_r(gdbl* Y, long ld, int rows, int c
     qr_panel_regs(Y, ld, rows, jp, nbp, red, taup, bc);
     if (fine) prof_mark(pr, *plast, 14);
   };
-  // panels (jp, jp+16), both full and register resident: T1, T2 and S21 = V2^T V1
-  auto factor_pair = [&](int jp, ldbl* T1, ldbl* tau1, ldbl* T2, ldbl* tau2, ldbl* S21) {
+  // panels (jp, jp+16), both full and register resident: T1, T2 and S21 = V2^T V1.  QR_QUAD: the Gram pass of each panel
+  // also forms the V^T C of the in-block update that follows it (qr_gram_multi), so that the reflectors are streamed once:
+  // V1^T C2 with the Gram of panel 1, and (quad: the two tiles behind the pair) V1^T C3, V2^T C3, V1^T C4, V2^T C4 -> big[512 ..]
+  // with the Gram of panel 2, for the pair's update (qr_tile_update2_all with W0 = big + 512)
+  auto factor_pair = [&](int jp, ldbl* T1, ldbl* tau1, ldbl* T2, ldbl* tau2, ldbl* S21, bool quad4) {
     factor_panel(jp, 16, T1, tau1);
-    qr_gram<false>(Y, ld, rows32, jp, jp, 16, jp, 16, jp, 16, big);
+    if (QR_QUAD) {
+      const int jc[2] = {jp, jp + 16}; const bool hd[2] = {true, false};
+      const int pa[2] = {0, 0}, pb[2] = {0, 1};
+      qr_gram_multi<2, 2>(Y, ld, rows32, jp, jc, hd, pa, pb, big);                           // G1, V1^T C2
+    } else qr_gram<false>(Y, ld, rows32, jp, jp, 16, jp, 16, jp, 16, big);
     if (fine) prof_mark(pr, *plast, 15);
     qr_T_from_gram(big, tau1, 16, T1);
     if (pr) prof_mark(pr, *plast, fine ? 16 : ph_panel);
-    qr_tile_update_all(Y, ld, rows32, jp, 16, jp + 16, T1, big);
+    qr_tile_update_all(Y, ld, rows32, jp, 16, jp + 16, T1, big, QR_QUAD ? big + 256 : nullptr);
     if (pr) prof_mark(pr, *plast, fine ? 17 : ph_trail);
     factor_panel(jp + 16, 16, T2, tau2);
-    qr_gram<true>(Y, ld, rows32, jp, jp + 16, 16, jp + 16, 16, jp, 16, big);   // V2^T V2 and S21 = V2^T V1 in one pass
+    if (QR_QUAD && quad4) {
+      const int jc[4] = {jp + 16, jp, jp + 32, jp + 48}; const bool hd[4] = {true, true, false, false};
+      const int pa[6] = {0, 0, 1, 0, 1, 0}, pb[6] = {0, 1, 2, 2, 3, 3};
+      qr_gram_multi<4, 6>(Y, ld, rows32, jp, jc, hd, pa, pb, big);
+    } else qr_gram<true>(Y, ld, rows32, jp, jp + 16, 16, jp + 16, 16, jp, 16, big);   // V2^T V2 and S21 = V2^T V1 in one pass
     for (int i = tid; i < 256; i += WG_THREADS) S21[i] = big[256 + i];
     if (fine) prof_mark(pr, *plast, 15);
     qr_T_from_gram(big, tau2, 16, T2);
@@ -1768,12 +1831,16 @@ __device__ __attribute__((noinline)) void qr_r(gdbl* Y, long ld, int rows, int c
   auto factor_pair2 = [&](int ja) {
     const int jc = ja + 32, jd = ja + 48;
     factor_panel(jc, 16, TsC, tauC);
-    { const int jy[3] = {jc, ja, ja + 16}; qr_gramN<3>(Y, ld, rows32, jc, jc, jy, big); }      // Gcc, Sca, Scb
+    {                                                                                          // Gcc, Sca, Scb, V_c^T C_d
+      const int jq[4] = {jc, ja, ja + 16, jd}; const bool hd[4] = {true, true, true, false};
+      const int pa[4] = {0, 0, 0, 0}, pb[4] = {0, 1, 2, 3};
+      qr_gram_multi<4, 4>(Y, ld, rows32, jc, jq, hd, pa, pb, big);
+    }
     for (int i = tid; i < 256; i += WG_THREADS) { Sca[i] = big[256 + i]; Scb[i] = big[512 + i]; }
     if (fine) prof_mark(pr, *plast, 15);
     qr_T_from_gram(big, tauC, 16, TsC);
     if (pr) prof_mark(pr, *plast, fine ? 16 : ph_panel);
-    qr_tile_update_all(Y, ld, rows32, jc, 16, jd, TsC, big);
+    qr_tile_update_all(Y, ld, rows32, jc, 16, jd, TsC, big, big + 768);
     if (pr) prof_mark(pr, *plast, fine ? 17 : ph_trail);
     factor_panel(jd, 16, TsD, tauD);
     { const int jy[4] = {jd, jc, ja, ja + 16}; qr_gramN<4>(Y, ld, rows32, jd, jd, jy, big); }  // Gdd, Sdc, Sda, Sdb
@@ -1797,8 +1864,8 @@ __device__ __attribute__((noinline)) void qr_r(gdbl* Y, long ld, int rows, int c
     const bool quad = QR_QUAD && fast && j0 + 64 <= kmax && j0 + 64 < cols;
     const bool pair = !quad && fast && j0 + 32 <= kmax && j0 + 32 < cols;
     if (quad) {
-      factor_pair(j0, Ts, tau, TsB, tauB, Sm);
-      qr_tile_update2_all<2>(Y, ld, rows32, j0, j0 + 32, Ts, TsB, Sm, big);
+      factor_pair(j0, Ts, tau, TsB, tauB, Sm, true);
+      qr_tile_update2_all<2>(Y, ld, rows32, j0, j0 + 32, Ts, TsB, Sm, big + 512);
       if (pr) prof_mark(pr, *plast, fine ? 17 : ph_trail);
       factor_pair2(j0);
       const ldbl* const Tq[4] = {Ts, TsB, TsC, TsD};
@@ -1827,7 +1894,7 @@ __device__ __attribute__((noinline)) void qr_r(gdbl* Y, long ld, int rows, int c
       j0 += 64;
       continue;
     }
-    if (pair) factor_pair(j0, Ts, tau, TsB, tauB, Sm);
+    if (pair) factor_pair(j0, Ts, tau, TsB, tauB, Sm, false);
     else {
       for (int i = tid; i < 256; i += WG_THREADS) Ts[i] = 0.0;
       if (tid < 16) tau[tid] = 0.0;
