@@ -236,6 +236,50 @@ int mpbp_set_profiling(mpbp_ctx* ctx, int32_t on);
  * phases in the order of wg::PH_* (csrc/wg_blocks.h). */
 int mpbp_phase_profile(mpbp_ctx* ctx, double* seconds, int32_t n, int32_t reset);
 
+/*
+ * SoftMargin importance sampler (reference src/sampling.jl:1-122, `SoftMarginSampler`, `onesample!`, `sample!`,
+ * `marginals`, `pair_marginals`, `autocorrelations`).  Trajectories are drawn from the prior dynamics of the context's
+ * factors and weighted by the observations and pair potentials:
+ *   x_i^0 ~ phi_i^0 / sum(phi_i^0)                              (src/sampling.jl:36-39; phi^0 is not in the weight)
+ *   x_i^{t+1} ~ w[i][t](. , x_nbrs^t, x_i^t), t = 0..T-1        (src/sampling.jl:41-49; recursive factors through the
+ *              functor of src/recursive_bp_factor.jl:33-45, generic factors through their dense table; the draw is
+ *              `sample_noalloc`, src/utils.jl:8-19: the first state whose running sum exceeds u)
+ *   log w = sum_{t>=1} sum_i log phi_i^t(x_i^t) + 1/2 sum_t sum_{directed (i,j)} log psi_ij^t(x_i^t, x_j^t)   (:46-53)
+ * Periodic contexts are sampled forward as onesample! does: w[i][T] is never read.
+ * Deliberate difference: the reference converts exp(log w) to a Float64 before storing it, so weights underflow to 0
+ * once log w < -745 (any sizeable graph with observations).  Here log w is kept throughout and the accumulators hold
+ * exp(log w - M) with M the running maximum, rescaled when M grows.
+ * Random numbers: Philox4x32-10 (Random123), key = the 64-bit seed, counter = (sample index lo, hi, t, node); one uniform
+ * per (sample, t, node), u = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53.  A trajectory depends only on (seed, global sample
+ * index): splitting mpbp_sample calls, or the device batch size, changes nothing.
+ * The sampler reads the context's CURRENT factors, node states, phi and psi at every mpbp_sample (the reference's
+ * `sms.bp` is a reference to the model); it must be destroyed before its context.  Graphs whose neighbour lists alias
+ * a node to itself (InfiniteRegularGraph) are refused with MPBP_EUNSUPPORTED, as are q > 4 and more than 32768 nodes.
+ */
+typedef struct mpbp_sampler mpbp_sampler;
+/* corr_nodes[n_corr]: sites whose two-time joints are accumulated (n_corr = 0: none), for t < u <= t + maxdist
+ * (maxdist outside 1..T: all) - `autocorrelations(f, sms; sites, maxdist)`, src/sampling.jl:155-183 */
+int mpbp_sampler_create(mpbp_sampler** out, mpbp_ctx* ctx, uint64_t seed, const int32_t* corr_nodes, int32_t n_corr,
+                        int32_t maxdist);
+void mpbp_sampler_destroy(mpbp_sampler* s);
+/* `sample!(sms, nsamples)` (src/sampling.jl:69-87): draws the next nsamples trajectories in device batches and folds
+ * them into the accumulators.  X: host [nsamples][T+1][n_nodes] uint8, 0-based states; logw: host [nsamples]; both may
+ * be NULL (the host then never holds the samples).  nsamples <= 0, or a node without a factor: MPBP_EINVAL. */
+int mpbp_sample(mpbp_sampler* s, int64_t nsamples, uint8_t* X, double* logw);
+/* `marginals(sms)` (src/sampling.jl:95-122): weighted proportions, layout of mpbp_beliefs.  MPBP_EINVAL if no sample
+ * has a nonzero weight. */
+int mpbp_sampler_marginals(mpbp_sampler* s, double* out);
+/* `pair_marginals(sms)` (src/sampling.jl:131-153): per directed edge, layout of mpbp_pair_beliefs (x_src fastest) */
+int mpbp_sampler_pair_marginals(mpbp_sampler* s, double* out);
+/* the weighted two-time joints behind `autocorrelations(f, sms)` (src/sampling.jl:155-183), layout of
+ * mpbp_twovar_marginals over the sites given at creation: out[k][t][u][x + q*y] = p(x^t = x, x^u = y), zero outside
+ * t < u <= t + maxdist.  MPBP_EINVAL if no sites were requested. */
+int mpbp_sampler_twovar_marginals(mpbp_sampler* s, double* out);
+/* samples drawn so far, log sum w and log sum w^2 (effective sample size = exp(2 log_sum_w - log_sum_w2)) */
+int mpbp_sampler_counts(mpbp_sampler* s, int64_t* nsamples, double* log_sum_w, double* log_sum_w2);
+/* the sampler's Philox4x32-10 block function on the host (known-answer checks): out = philox(counter[4], key[2]) */
+int mpbp_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+
 /* Self-test entry points used by tests/ (device building blocks against host references). */
 int mpbp_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const double* A, const double* B,
                        double* C);

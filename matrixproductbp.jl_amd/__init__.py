@@ -12,3 +12,5 @@ from .mpbp import (CB_BP, MPBP, random_message, periodic_mpbp, periodic_mpbp_inf
                    onebpiter, pair_beliefs, reset_messages, pair_beliefs_as_mpem, pair_correlations,
                    alternate_marginals, alternate_correlations, expectation, logprob, reset, reset_observations,
                    is_free_dynamics)
+from .sampling import (SoftMarginSampler, draw_node_observations, effective_sample_size, marginals, mean_with_uncertainty,
+                       onesample, pair_marginals, sample)

@@ -9,7 +9,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmpbp_hip.so")
-SOURCES = ["mpbp_hip.hip", "v2_engine.hip"]
+SOURCES = ["mpbp_hip.hip", "v2_engine.hip", "sampler.hip"]
 
 
 def headers():
@@ -56,7 +56,9 @@ EXPORTS = ["mpbp_create", "mpbp_destroy", "mpbp_last_error", "mpbp_slab_layout",
            "mpbp_set_factor", "mpbp_set_generic_factor", "mpbp_set_node_states", "mpbp_set_phi", "mpbp_set_psi", "mpbp_set_messages", "mpbp_get_bonds",
            "mpbp_get_messages", "mpbp_reset_messages", "mpbp_sweep", "mpbp_beliefs", "mpbp_get_belief_train", "mpbp_pair_beliefs",
            "mpbp_free_energy", "mpbp_logz", "mpbp_allgather_slots", "mpbp_twovar_marginals", "mpbp_set_profiling", "mpbp_phase_profile", "mpbp_selftest_gemm", "mpbp_selftest_qr", "mpbp_selftest_qr_bench",
-           "mpbp_selftest_jacobi_bench", "mpbp_selftest_svd", "mpbp_selftest_qr_batched", "mpbp_selftest_qr_batched_seq", "mpbp_selftest_jacobi_grid", "mpbp_selftest_jacobi_block"]
+           "mpbp_selftest_jacobi_bench", "mpbp_selftest_svd", "mpbp_selftest_qr_batched", "mpbp_selftest_qr_batched_seq", "mpbp_selftest_jacobi_grid", "mpbp_selftest_jacobi_block",
+           "mpbp_sampler_create", "mpbp_sampler_destroy", "mpbp_sample", "mpbp_sampler_marginals",
+           "mpbp_sampler_pair_marginals", "mpbp_sampler_twovar_marginals", "mpbp_sampler_counts", "mpbp_philox4x32_10"]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -142,6 +144,16 @@ def lib():
     L.mpbp_selftest_jacobi_block.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, C.c_int32, ip]
     L.mpbp_selftest_qr_batched.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, dp, dp]
     L.mpbp_selftest_qr_batched_seq.argtypes = [C.c_int32, C.c_int32, ip, C.c_int32, dp, dp, ip]
+    u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    L.mpbp_sampler_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, ip, C.c_int32, C.c_int32]
+    L.mpbp_sampler_destroy.argtypes = [C.c_void_p]
+    L.mpbp_sampler_destroy.restype = None
+    L.mpbp_sample.argtypes = [C.c_void_p, C.c_int64, u8p, dp]
+    L.mpbp_sampler_marginals.argtypes = [C.c_void_p, dp]
+    L.mpbp_sampler_pair_marginals.argtypes = [C.c_void_p, dp]
+    L.mpbp_sampler_twovar_marginals.argtypes = [C.c_void_p, dp]
+    L.mpbp_sampler_counts.argtypes = [C.c_void_p, lp, dp, dp]
+    L.mpbp_philox4x32_10.argtypes = [u32p, u32p, u32p]
     _lib = L
     return L
 

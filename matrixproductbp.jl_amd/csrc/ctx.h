@@ -83,6 +83,7 @@ struct mpbp_ctx {
   double* d_one = nullptr; int32_t* d_ones = nullptr; double* d_ident = nullptr; int ident_n = 0;
   // tables
   bool tables_dirty = true;
+  uint64_t version = 0;            // bumped by every input setter (factors, node states, phi, psi): the sampler refreshes its tables on change
   double* d_tab = nullptr; size_t tab_doubles = 0;
   std::vector<int64_t> pxy_off;    // per neighbour position
   std::vector<int64_t> pxy_tstride;

@@ -164,7 +164,7 @@ extern "C" int mpbp_set_factor(mpbp_ctx* c, int32_t node, int32_t deg, const int
   f.prob_xy.assign(prob_xy, prob_xy + xy_sz * nt);
   f.prob_yy.assign(prob_yy, prob_yy + off * nt);
   f.prob_y0.assign(prob_y0, prob_y0 + (int64_t)f.ny[0] * q * nt);
-  c->tables_dirty = true;
+  c->tables_dirty = true; c->version++;
   return MPBP_OK;
 }
 
@@ -193,7 +193,7 @@ extern "C" int mpbp_set_generic_factor(mpbp_ctx* c, int32_t node, int32_t deg, i
   f = NodeFactor{};
   f.set = true; f.generic = true; f.deg = deg; f.nt = nt;
   f.gen_w.assign(w, w + sz * nt);
-  c->tables_dirty = true;
+  c->tables_dirty = true; c->version++;
   return MPBP_OK;
 }
 
@@ -206,17 +206,17 @@ extern "C" int mpbp_set_node_states(mpbp_ctx* c, const int32_t* q_node) {
   }
   c->qnode.assign(q_node, q_node + c->N);
   c->hetero_q = het;
-  c->tables_dirty = true;
+  c->tables_dirty = true; c->version++;
   return mpbp_reset_messages(c);          // the initial messages are uniform over the REAL states of both end nodes
 }
 
 extern "C" int mpbp_set_phi(mpbp_ctx* c, const double* phi) {
   if (!c || !phi) return MPBP_EINVAL;
-  c->phi.assign(phi, phi + (size_t)c->q * c->L * c->N); c->tables_dirty = true; return MPBP_OK;
+  c->phi.assign(phi, phi + (size_t)c->q * c->L * c->N); c->tables_dirty = true; c->version++; return MPBP_OK;
 }
 extern "C" int mpbp_set_psi(mpbp_ctx* c, const double* psi) {
   if (!c || !psi) return MPBP_EINVAL;
-  c->psi.assign(psi, psi + (size_t)c->q * c->q * c->L * c->E); c->tables_dirty = true; return MPBP_OK;
+  c->psi.assign(psi, psi + (size_t)c->q * c->q * c->L * c->E); c->tables_dirty = true; c->version++; return MPBP_OK;
 }
 
 extern "C" int mpbp_set_messages(mpbp_ctx* c, const int32_t* bonds, const int64_t* offsets, const double* data) {

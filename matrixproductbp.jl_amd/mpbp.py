@@ -550,7 +550,11 @@ def beliefs_tu(bp: MPBP, sites=None, maxdist=None):
 
 def autocorrelations(f, bp: MPBP, sites=None, maxdist=None):
     """src/mpbp.jl:245-255: `r[i][t, u] = <f(x_i^t) f(x_i^u)>` for t < u (0 elsewhere); the O(T^2) two-time
-    marginals come from the device (mpbp_twovar_marginals), only the q x q contraction with f runs here."""
+    marginals come from the device (mpbp_twovar_marginals), only the q x q contraction with f runs here.
+    For a `SoftMarginSampler` the sampled form (sampling.autocorrelations) is returned."""
+    from . import sampling
+    if isinstance(bp, sampling.SoftMarginSampler):
+        return sampling.autocorrelations(f, bp, sites, maxdist)
     sites = list(range(bp.g.nv())) if sites is None else list(sites)
     L, q = bp.T + 1, bp.q
     nodes = np.ascontiguousarray(sites, dtype=np.int32)
@@ -567,15 +571,21 @@ def autocorrelations(f, bp: MPBP, sites=None, maxdist=None):
 
 
 def autocovariances(f, bp: MPBP, sites=None, maxdist=None):
-    """src/mpbp.jl:288-294: `r - mu mu'`."""
+    """src/mpbp.jl:288-294: `r - mu mu'`.  For a `SoftMarginSampler`: sampling.autocovariances."""
+    from . import sampling
+    if isinstance(bp, sampling.SoftMarginSampler):
+        return sampling.autocovariances(f, bp, sites, maxdist)
     sites = list(range(bp.g.nv())) if sites is None else list(sites)
     mu = means(f, bp)
     r = autocorrelations(f, bp, sites, maxdist)
     return [ri - np.outer(mu[i], mu[i]) for ri, i in zip(r, sites)]
 
 
-def means(f, bp: MPBP):
-    """src/mpbp.jl:257-261 (`f(x, i)` with the 1-based state x)."""
+def means(f, bp: MPBP, sites=None):
+    """src/mpbp.jl:257-261 (`f(x, i)` with the 1-based state x).  For a `SoftMarginSampler`: sampling.means."""
+    from . import sampling
+    if isinstance(bp, sampling.SoftMarginSampler):
+        return sampling.means(f, bp, sites)
     b = beliefs(bp)
     return [[sum(f(x + 1, i) * p[x] for x in range(len(p))) for p in bi] for i, bi in enumerate(b)]
 
