@@ -451,10 +451,52 @@ static int build_tables(mpbp_ctx* c) {
 // ================================================================================================
 // the sweep
 // ================================================================================================
+// returns the MPBP_* code of a failed step (HIPCHK's counterpart for calls that report one)
+#define RCCHK(call) do { const int rc_ = (call); if (rc_ != MPBP_OK) return rc_; } while (0)
+
 namespace {
 
+enum Form { FORM_AUTO, FORM_GRID, FORM_WG };   // MPBP_GAUGE / MPBP_SWEEP2 = grid | wg
+
+// Debug and tuning switches of a sweep, read from the environment once per mpbp_sweep call: tests switch them between
+// calls, so they are never cached for the process.
+struct SweepEnv {
+  int split_nodes = 0;          // MPBP_DEBUG_SPLIT_NODES=k: take the split path whenever a pass lists more than k nodes
+  bool force_generic = false;   // MPBP_DEBUG_FORCE_GENERIC=1: the large-problem engine paths on small inputs (plan_cfg)
+  bool no_small = false;        // MPBP_DEBUG_NO_SMALL=1: every engine problem to the 512-thread variant
+  bool force_small = false;     // MPBP_DEBUG_FORCE_SMALL: few single-wave problems stay on the single-wave variant
+  bool no_pack = false;         // MPBP_DEBUG_NO_PACK: cavity launches level by level instead of by readiness
+  bool coop_fail_once = false;  // MPBP_DEBUG_COOP_FAIL_ONCE: pretend that a batch's first gauge sweep timed out
+  Form gauge = FORM_AUTO, sweep2 = FORM_AUTO;   // MPBP_GAUGE, MPBP_SWEEP2: force where sweeps 1 and 2 run
+};
+static SweepEnv read_sweep_env() {
+  auto set = [](const char* name) { return getenv(name) != nullptr; };
+  auto is1 = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+  auto form = [](const char* name) { const char* e = getenv(name); return !e ? FORM_AUTO : !strcmp(e, "grid") ? FORM_GRID : !strcmp(e, "wg") ? FORM_WG : FORM_AUTO; };
+  const char* split = getenv("MPBP_DEBUG_SPLIT_NODES");
+  return SweepEnv{split ? atoi(split) : 0, is1("MPBP_DEBUG_FORCE_GENERIC"), is1("MPBP_DEBUG_NO_SMALL"), set("MPBP_DEBUG_FORCE_SMALL"),
+                  set("MPBP_DEBUG_NO_PACK"), set("MPBP_DEBUG_COOP_FAIL_ONCE"), form("MPBP_GAUGE"), form("MPBP_SWEEP2")};
+}
+// what the stages of one pass share: the context, the switches, the truncation and the timers of the cavity launches
+struct Pass {
+  mpbp_ctx* c; const SweepEnv& env; mpbp_trunc trunc; double damp;
+  float ms_orth = 0.f; int n_orth = 0;
+};
 struct OpRec { int in1, in2, out, d1, d2, node, level; };   // indices into the train table
 
+// ---------------------------------------------------------------- the plan of a pass: trains, ops, levels
+struct TrainSpec { int cap, ny, qphys; int d; int level; int64_t tab_off; bool is_init; int node; int kron_skip = -2; };   // kron_skip >= -1: product of the node's in-messages except that position (generic factors)
+struct NodePlan { int node; std::vector<int> src, dest; int full; int init; };
+// finalisation trains: ctilde (bond 2*cap... = q*cap), engine output (message), belief ctilde
+struct FinRec { int k, j, p, src, ct, out; int nrm = -1, sum = -1, out2 = -1, occ = 0; bool gen = false; };
+struct SweepPlan {
+  std::vector<TrainSpec> specs;     // scratch trains to allocate
+  std::vector<OpRec> ops;
+  std::vector<NodePlan> plans;
+  std::vector<FinRec> fins, bels;
+  int maxlevel = 0;
+  bool any_generic = false;
+};
 // a pair of HIP events that is destroyed on every exit path
 struct EventPair {
   hipEvent_t a = nullptr, b = nullptr;
@@ -474,15 +516,15 @@ struct EngLaunchPlan {
 // A problem goes to the single-wave engine when every QR panel of its first sweep fits the register panel of
 // one wave (rows of Y_t = B*ny*q <= QR_RS*64): these are the latency-bound problems (finalisation, products with
 // the bond-1 initial train, low bond dimensions).  MPBP_DEBUG_NO_SMALL=1 sends everything to the 512-thread one.
-static inline bool small_problem(int64_t B, int ny, int q) {
-  const bool off = [] { const char* e = getenv("MPBP_DEBUG_NO_SMALL"); return e && e[0] == '1'; }();
-  return !off && B * ny * q <= v64::wg::QR_RS * 64;
+static inline bool small_problem(const SweepEnv& env, int64_t B, int ny, int q) {
+  return !env.no_small && B * ny * q <= v64::wg::QR_RS * 64;
 }
 
 static inline int r16h(int x) { return (x + 15) & ~15; }
+static size_t free_bytes() { size_t freeb = 0, totb = 0; hipMemGetInfo(&freeb, &totb); return freeb; }
 
 // fills cfg + returns LDS bytes and per-slot scratch doubles
-static void plan_cfg(const EngLaunchPlan& pl, int L, mpbp_trunc trunc, EngCfg& cfg, size_t& lds_bytes) {
+static void plan_cfg(const EngLaunchPlan& pl, int L, mpbp_trunc trunc, bool force_generic, EngCfg& cfg, size_t& lds_bytes) {
   memset(&cfg, 0, sizeof cfg);
   cfg.L = L; cfg.trunc = trunc;
   const int64_t Bmax = (int64_t)pl.cap1 * pl.cap2;
@@ -522,12 +564,10 @@ static void plan_cfg(const EngLaunchPlan& pl, int L, mpbp_trunc trunc, EngCfg& c
   const int64_t coresE = ((nA1 + 3) & ~3) + ((nA2 + 3) & ~3) + ((nE + 3) & ~3);
   // JA only (V is not accumulated): [Rr | 1] x min(r1, Rr) with Rr <= nmax, r1 <= Bmax
   const int64_t jac = (((int64_t)(nmax + 1) * std::min<int64_t>(nmax, Bmax) + 3) & ~3);
-  // MPBP_DEBUG_FORCE_GENERIC=1 forces the large-problem paths (operands in global memory, global QR panel)
-  // on small inputs so that tests can cover them
-  const char* dbg = getenv("MPBP_DEBUG_FORCE_GENERIC");
-  const bool force = dbg && dbg[0] == '1';
-  cfg.force_generic = force ? 1 : 0;
-  bool cores_fit = !force && base + coresE <= budget, jac_fit = !force && base + jac <= budget;
+  // force_generic (MPBP_DEBUG_FORCE_GENERIC=1) takes the large-problem paths (operands in global memory, global QR
+  // panel) on small inputs so that tests can cover them
+  cfg.force_generic = force_generic ? 1 : 0;
+  bool cores_fit = !force_generic && base + coresE <= budget, jac_fit = !force_generic && base + jac <= budget;
   if (cores_fit) { int64_t o = base; cfg.lds_A1c = (int32_t)o; o += (nA1 + 3) & ~3; cfg.lds_A2c = (int32_t)o; o += (nA2 + 3) & ~3; cfg.lds_E = (int32_t)o; }
   else { cfg.lds_A1c = cfg.lds_A2c = cfg.lds_E = -1; }
   if (jac_fit) { cfg.lds_JA = (int32_t)base; cfg.lds_JV = -1; }
@@ -542,21 +582,98 @@ static void plan_cfg(const EngLaunchPlan& pl, int L, mpbp_trunc trunc, EngCfg& c
 
 }  // namespace
 
-static int launch_engine_impl(mpbp_ctx* c, EngLaunchPlan& pl, mpbp_trunc trunc, bool count_as_orth, float* ms_orth, int* n_orth);
-// MPBP_V2_TIMING=1: wall time of every engine launch (host planning + device, stream drained) on stderr
-static int launch_engine(mpbp_ctx* c, EngLaunchPlan& pl, mpbp_trunc trunc, bool count_as_orth, float* ms_orth, int* n_orth) {
-  static const bool tm = getenv("MPBP_V2_TIMING") != nullptr;
-  if (!tm) return launch_engine_impl(c, pl, trunc, count_as_orth, ms_orth, n_orth);
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = launch_engine_impl(c, pl, trunc, count_as_orth, ms_orth, n_orth);
-  (void)hipStreamSynchronize(c->stream);
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  bool mir = false; for (const EngProb& P : pl.probs) mir = mir || P.mirror;
-  fprintf(stderr, "[engine launch] nprob=%zu caps=%dx%d->%d ny=%d q=%d small=%d grid=%d mirror=%d cavity=%d  %10.1f ms\n", pl.probs.size(), pl.cap1, pl.cap2,
-          pl.capout, pl.ny, pl.q, (int)pl.small, (int)pl.ext, (int)mir, (int)count_as_orth, ms);
-  return rc;
+// ---------------------------------------------------------------- engine launches
+// The engine variant (pl.small) and where sweep 1 runs (pl.ext) of a launch.
+static void choose_variant(const Pass& ps, EngLaunchPlan& pl, int64_t bmact) {
+  const mpbp_ctx* c = ps.c;
+  const int nprob = (int)pl.probs.size();
+  if (!pl.small && !ps.env.no_small && (int64_t)pl.cap1 * pl.cap2 * pl.ny * pl.q <= v64::wg::QR_RS * 64 && nprob > 2 * c->num_cu) pl.small = true;
+  // few single-wave problems (at most two rounds of 512-thread workgroups): the 512-thread engine finishes them
+  // sooner, a single wave per problem only pays off when there are enough problems to fill 4 of them per CU
+  // (MPBP_DEBUG_FORCE_SMALL=1 keeps them on the single-wave engine so that small tests cover it)
+  if (pl.small && nprob <= 2 * c->num_cu && !ps.env.force_small) pl.small = false;
+  // Where sweep 1 runs: in the problem's own workgroup (slot-resident Lf stack), or as the batched, grid-level gauge
+  // sweep of v2_engine.hip.  MPBP_GAUGE=grid|wg forces one; otherwise the grid form is taken when a workgroup cannot
+  // hold the problem (Y_t beyond one register panel's rows) or its slot would be huge.
+  bool grid = false;
+  if (!pl.small) {
+    const int64_t Bm = (int64_t)pl.cap1 * pl.cap2;
+    if (ps.env.gauge != FORM_AUTO) grid = ps.env.gauge == FORM_GRID;
+    else grid = bmact * pl.ny * pl.q > 2048 || Bm * Bm * (c->L + 1) * 8 > (int64_t)256 << 20;
+    for (const EngProb& P : pl.probs) if (P.mirror) grid = false;
+  }
+  pl.ext = grid;
 }
-static int launch_engine_impl(mpbp_ctx* c, EngLaunchPlan& pl, mpbp_trunc trunc, bool count_as_orth, float* ms_orth, int* n_orth) {
+// One launch of the workgroup engine over ps[0 .. np): as many slots as fit the scratch budget.  e0 (optional) is
+// recorded right before the kernel.
+static int launch_slots(Pass& ps, const EngLaunchPlan& pl, const EngProb* probs, int np, bool cavity, hipEvent_t e0) {
+  mpbp_ctx* c = ps.c;
+  EngCfg cfg; size_t lds_bytes;
+  plan_cfg(pl, c->L, ps.trunc, ps.env.force_generic, cfg, lds_bytes);
+  // phase timers cover the 512-thread cavity launches; MPBP_PROF_SMALL=1 covers the single-wave launches instead
+  static const bool prof_small = [] { const char* e = getenv("MPBP_PROF_SMALL"); return e && e[0] == '1'; }();
+  cfg.prof = (c->profiling >= 2 && (prof_small ? pl.small : cavity)) ? c->d_prof : nullptr;
+  auto kern = pl.small ? v64::eng_kernel : v512::eng_kernel;
+  const int nthreads = pl.small ? 64 : 512;
+  HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  int per_cu = 1;
+  hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, nthreads, lds_bytes);
+  if (per_cu < 1) per_cu = 1;
+  int nslots = std::min(np, c->num_cu * per_cu);
+  // scratch: bounded by a budget; fewer slots if needed
+  size_t slot_bytes = (size_t)cfg.slot_doubles * 8;
+  size_t budget = c->scratch.cap + (size_t)(free_bytes() * 0.85);
+  while (nslots > 1 && (size_t)nslots * slot_bytes > budget) nslots = (nslots + 1) / 2;
+  RCCHK(ensure_arena(c, c->scratch, (size_t)nslots * slot_bytes + sizeof(EngProb) * np + 4096));
+  double* d_scr = (double*)c->scratch.base;
+  EngProb* d_probs = (EngProb*)(c->scratch.base + (((size_t)nslots * slot_bytes + 255) & ~size_t(255)));
+  HIPCHK(c, hipMemcpyAsync(d_probs, probs, sizeof(EngProb) * np, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(int), c->stream));
+  if (e0) hipEventRecord(e0, c->stream);      // the workgroup form is timed kernel only (host planning excluded)
+  hipLaunchKernelGGL(kern, dim3(nslots), dim3(nthreads), lds_bytes, c->stream, d_probs, np, c->d_counter, cfg, d_scr, c->d_stats);
+  HIPCHK(c, hipGetLastError());
+  return MPBP_OK;
+}
+// Sweep 1 as the batched gauge sweep, batch by batch, each followed by sweep 2 on the grid or in the workgroup engine.
+static int launch_grid(Pass& ps, const EngLaunchPlan& pl, std::vector<EngProb>& probs, const std::vector<int32_t>& hb, int64_t bmact, bool cavity) {
+  mpbp_ctx* c = ps.c;
+  const int nprob = (int)probs.size();
+  const bool plannable = ps.trunc.kind == MPBP_TRUNC_BOND || ps.trunc.kind == MPBP_TRUNC_BOND_MAX;
+  // The truncating sweep goes to the grid as well when its ranks are plannable (TruncBond / TruncBondMax) and a time
+  // step is heavy enough to pay for its launches (M_t = N_t Lf_{t+1} of >= 0.2 Gflop); else it runs in the
+  // workgroup engine on the factors just computed.  MPBP_SWEEP2=grid|wg forces one.
+  bool s2grid = plannable && 2.0 * (double)bmact * (double)bmact * pl.capout * pl.ny * pl.q >= 2e8;
+  if (ps.env.sweep2 != FORM_AUTO) s2grid = plannable && ps.env.sweep2 == FORM_GRID;
+  for (int done = 0; done < nprob;) {
+    int nd = 0, did2 = 0;
+    // The cooperative panel kernel (k_colsteps_coop) assumes that this process owns the GPU: its row-chunk workgroups
+    // wait for each other inside one launch.  If they are not co-resident (a second process or stream on the device)
+    // an arrival counter times out; the kernel then leaves Y untouched and raises a flag.  Nothing of a batch is
+    // committed to the message slab before this point (products live in the work arena), so the batch is simply
+    // repeated with one launch per column step, and the context stays in that mode.
+    for (int attempt = 0;; attempt++) {
+      EngStats sbak;
+      const bool may_retry = !c->no_coop_panel;
+      if (may_retry) HIPCHK(c, hipMemcpyAsync(&sbak, c->d_stats, sizeof sbak, hipMemcpyDeviceToHost, c->stream));
+      RCCHK(v2_gauge_sweep(c, probs.data() + done, nprob - done, hb.data() + (size_t)done * 2 * (c->L + 1), s2grid ? &ps.trunc : nullptr, &nd, &did2));
+      if (!did2) RCCHK(launch_slots(ps, pl, probs.data() + done, nd, cavity, nullptr));
+      // the triangular factors live in c->v2arena until sweep 2 has consumed them
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      int herr = 0;
+      HIPCHK(c, hipMemcpy(&herr, c->d_counter + 8, sizeof(int), hipMemcpyDeviceToHost));
+      if (ps.env.coop_fail_once && may_retry && attempt == 0) herr = 1;      // test hook: pretend the first attempt timed out
+      if (!herr) break;
+      if (!may_retry) return c->fail(MPBP_EHIP, "batched gauge sweep: arrival counter timed out although the cooperative panel kernel was not used");
+      c->no_coop_panel = true;
+      HIPCHK(c, hipMemcpy(c->d_stats, &sbak, sizeof sbak, hipMemcpyHostToDevice));    // the repeated batch counts once
+    }
+    done += nd;
+  }
+  return MPBP_OK;
+}
+// cavity: a 512-thread cavity product (counted in ms_orth / n_orth when the context is profiling)
+static int launch_engine_impl(Pass& ps, EngLaunchPlan& pl, bool cavity) {
+  mpbp_ctx* c = ps.c;
   const int nprob = (int)pl.probs.size();
   if (nprob == 0) return MPBP_OK;
   // sort by decreasing cost (longest first)
@@ -569,195 +686,159 @@ static int launch_engine_impl(mpbp_ctx* c, EngLaunchPlan& pl, mpbp_trunc trunc, 
   // copy of their bond tables lets the launch be sized by the real dimensions: during the first sweeps (bonds 1, 2, 4,
   // ...) a "large" level is really a batch of small problems, and slots sized by max_bond^4 would be wasted.
   std::vector<int32_t> hb;
-  {
-    int rc = v2_gather_bonds(c, sorted.data(), nprob, hb);
-    if (rc != MPBP_OK) return rc;
-  }
+  RCCHK(v2_gather_bonds(c, sorted.data(), nprob, hb));
+  const int L1 = c->L + 1;
   int a1 = 1, a2 = 1; int64_t bmact = 1;
-  {
-    const int L1 = c->L + 1;
-    for (int i = 0; i < nprob; i++) {
-      const int32_t* b1 = hb.data() + (size_t)i * 2 * L1; const int32_t* b2 = b1 + L1;
-      for (int t = 0; t < L1; t++) { a1 = std::max(a1, (int)b1[t]); a2 = std::max(a2, (int)b2[t]); bmact = std::max<int64_t>(bmact, (int64_t)b1[t] * b2[t]); }
-    }
-    pl.cap1 = std::min(pl.cap1, a1); pl.cap2 = std::min(pl.cap2, a2);
+  for (int i = 0; i < nprob; i++) {
+    const int32_t* b1 = hb.data() + (size_t)i * 2 * L1; const int32_t* b2 = b1 + L1;
+    for (int t = 0; t < L1; t++) { a1 = std::max(a1, (int)b1[t]); a2 = std::max(a2, (int)b2[t]); bmact = std::max<int64_t>(bmact, (int64_t)b1[t] * b2[t]); }
   }
-  const bool no_small = [] { const char* e = getenv("MPBP_DEBUG_NO_SMALL"); return e && e[0] == '1'; }();
-  if (!pl.small && !no_small && (int64_t)pl.cap1 * pl.cap2 * pl.ny * pl.q <= v64::wg::QR_RS * 64 && nprob > 2 * c->num_cu) pl.small = true;
-  // few single-wave problems (at most two rounds of 512-thread workgroups): the 512-thread engine finishes them
-  // sooner, a single wave per problem only pays off when there are enough problems to fill 4 of them per CU
-  // (MPBP_DEBUG_FORCE_SMALL=1 keeps them on the single-wave engine so that small tests cover it)
-  if (pl.small && nprob <= 2 * c->num_cu && !getenv("MPBP_DEBUG_FORCE_SMALL")) pl.small = false;
-  // Where sweep 1 runs: in the problem's own workgroup (slot-resident Lf stack), or as the batched, grid-level gauge
-  // sweep of v2_engine.hip.  MPBP_GAUGE=grid|wg forces one; otherwise the grid form is taken when a workgroup cannot
-  // hold the problem (Y_t beyond one register panel's rows) or its slot would be huge.
-  bool grid = false;
-  if (!pl.small) {
-    const int64_t Bm = (int64_t)pl.cap1 * pl.cap2;
-    const char* gm = getenv("MPBP_GAUGE");
-    if (gm && !strcmp(gm, "grid")) grid = true;
-    else if (gm && !strcmp(gm, "wg")) grid = false;
-    else grid = bmact * pl.ny * pl.q > 2048 || Bm * Bm * (c->L + 1) * 8 > (int64_t)256 << 20;
-    for (const EngProb& P : sorted) if (P.mirror) grid = false;
-  }
-  pl.ext = grid;
-  hipEvent_t e0_at_kernel = nullptr;
-  auto run = [&](EngProb* ps, int np) -> int {
-    EngCfg cfg; size_t lds_bytes;
-    plan_cfg(pl, c->L, trunc, cfg, lds_bytes);
-    // phase timers cover the 512-thread cavity launches; MPBP_PROF_SMALL=1 covers the single-wave launches instead
-    static const bool prof_small = [] { const char* e = getenv("MPBP_PROF_SMALL"); return e && e[0] == '1'; }();
-    cfg.prof = (c->profiling >= 2 && (prof_small ? pl.small : count_as_orth)) ? c->d_prof : nullptr;
-    const void* kern = pl.small ? (const void*)v64::eng_kernel : (const void*)v512::eng_kernel;
-    const int nthreads = pl.small ? 64 : 512;
-    HIPCHK(c, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    int per_cu = 1;
-    if (pl.small) hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v64::eng_kernel, nthreads, lds_bytes);
-    else hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, v512::eng_kernel, nthreads, lds_bytes);
-    if (per_cu < 1) per_cu = 1;
-    int nslots = std::min(np, c->num_cu * per_cu);
-    // scratch: bounded by a budget; fewer slots if needed
-    size_t slot_bytes = (size_t)cfg.slot_doubles * 8;
-    size_t freeb = 0, totb = 0;
-    hipMemGetInfo(&freeb, &totb);
-    size_t budget = c->scratch.cap + (size_t)(freeb * 0.85);
-    while (nslots > 1 && (size_t)nslots * slot_bytes > budget) nslots = (nslots + 1) / 2;
-    int rc = ensure_arena(c, c->scratch, (size_t)nslots * slot_bytes + sizeof(EngProb) * np + 4096);
-    if (rc != MPBP_OK) return rc;
-    double* d_scr = (double*)c->scratch.base;
-    EngProb* d_probs = (EngProb*)(c->scratch.base + (((size_t)nslots * slot_bytes + 255) & ~size_t(255)));
-    HIPCHK(c, hipMemcpyAsync(d_probs, ps, sizeof(EngProb) * np, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(int), c->stream));
-    if (e0_at_kernel) hipEventRecord(e0_at_kernel, c->stream);      // the workgroup form is timed kernel only (host planning excluded)
-    if (pl.small) hipLaunchKernelGGL(v64::eng_kernel, dim3(nslots), dim3(64), lds_bytes, c->stream, d_probs, np, c->d_counter, cfg, d_scr, c->d_stats);
-    else hipLaunchKernelGGL(v512::eng_kernel, dim3(nslots), dim3(512), lds_bytes, c->stream, d_probs, np, c->d_counter, cfg, d_scr, c->d_stats);
-    (void)kern;
-    HIPCHK(c, hipGetLastError());
-    return MPBP_OK;
-  };
-  const bool timed = count_as_orth && c->profiling;
+  pl.cap1 = std::min(pl.cap1, a1); pl.cap2 = std::min(pl.cap2, a2);
+  choose_variant(ps, pl, bmact);
+  const bool timed = cavity && c->profiling;
   EventPair lev;
   hipEvent_t e0 = timed ? lev.a : nullptr, e1 = lev.b;
-  e0_at_kernel = (timed && !grid) ? e0 : nullptr;
-  if (timed && grid) hipEventRecord(e0, c->stream);                 // batched form: gauge sweep + sweep 2 together
-  if (!grid) {
-    int rc = run(sorted.data(), nprob);
-    if (rc != MPBP_OK) return rc;
-  } else {
-    for (int done = 0; done < nprob;) {
-      int nd = 0;
-      // The truncating sweep goes to the grid as well when its ranks are plannable (TruncBond / TruncBondMax) and a time
-      // step is heavy enough to pay for its launches (M_t = N_t Lf_{t+1} of >= 0.2 Gflop); else it runs in the
-      // workgroup engine on the factors just computed.  MPBP_SWEEP2=grid|wg forces one.
-      bool s2grid = (trunc.kind == MPBP_TRUNC_BOND || trunc.kind == MPBP_TRUNC_BOND_MAX) &&
-                    2.0 * (double)bmact * (double)bmact * pl.capout * pl.ny * pl.q >= 2e8;
-      if (const char* s2 = getenv("MPBP_SWEEP2")) { if (!strcmp(s2, "grid")) s2grid = trunc.kind == MPBP_TRUNC_BOND || trunc.kind == MPBP_TRUNC_BOND_MAX; else if (!strcmp(s2, "wg")) s2grid = false; }
-      int did2 = 0;
-      // The cooperative panel kernel (k_colsteps_coop) assumes that this process owns the GPU: its row-chunk workgroups
-      // wait for each other inside one launch.  If they are not co-resident (a second process or stream on the device)
-      // an arrival counter times out; the kernel then leaves Y untouched and raises a flag.  Nothing of a batch is
-      // committed to the message slab before this point (products live in the work arena), so the batch is simply
-      // repeated with one launch per column step, and the context stays in that mode.
-      for (int attempt = 0;; attempt++) {
-        EngStats sbak;
-        const bool may_retry = !c->no_coop_panel;
-        if (may_retry) HIPCHK(c, hipMemcpyAsync(&sbak, c->d_stats, sizeof sbak, hipMemcpyDeviceToHost, c->stream));
-        int rc = v2_gauge_sweep(c, sorted.data() + done, nprob - done, hb.data() + (size_t)done * 2 * (c->L + 1), s2grid ? &trunc : nullptr, &nd, &did2);
-        if (rc != MPBP_OK) return rc;
-        if (!did2) {
-          rc = run(sorted.data() + done, nd);
-          if (rc != MPBP_OK) return rc;
-        }
-        // the triangular factors live in c->v2arena until sweep 2 has consumed them
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        int herr = 0;
-        HIPCHK(c, hipMemcpy(&herr, c->d_counter + 8, sizeof(int), hipMemcpyDeviceToHost));
-        const bool inject = getenv("MPBP_DEBUG_COOP_FAIL_ONCE") != nullptr;            // test hook: pretend the first attempt timed out
-        if (inject && may_retry && attempt == 0) herr = 1;
-        if (!herr) break;
-        if (!may_retry) return c->fail(MPBP_EHIP, "batched gauge sweep: arrival counter timed out although the cooperative panel kernel was not used");
-        c->no_coop_panel = true;
-        HIPCHK(c, hipMemcpy(c->d_stats, &sbak, sizeof sbak, hipMemcpyHostToDevice));    // the repeated batch counts once
-      }
-      done += nd;
-    }
-  }
+  if (timed && pl.ext) hipEventRecord(e0, c->stream);                 // batched form: gauge sweep + sweep 2 together
+  RCCHK(pl.ext ? launch_grid(ps, pl, sorted, hb, bmact, cavity) : launch_slots(ps, pl, sorted.data(), nprob, cavity, e0));
   if (e0) {
     hipEventRecord(e1, c->stream); hipEventSynchronize(e1);
-    float ms = 0; hipEventElapsedTime(&ms, e0, e1); *ms_orth += ms; *n_orth += 1;
+    float ms = 0; hipEventElapsedTime(&ms, e0, e1); ps.ms_orth += ms; ps.n_orth += 1;
   }
   // the host vectors `sorted` must outlive the async copy
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return MPBP_OK;
 }
-
+// MPBP_V2_TIMING=1: wall time of every engine launch (host planning + device, stream drained) on stderr
+static int launch_engine(Pass& ps, EngLaunchPlan& pl, bool cavity) {
+  static const bool tm = getenv("MPBP_V2_TIMING") != nullptr;
+  if (!tm) return launch_engine_impl(ps, pl, cavity);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = launch_engine_impl(ps, pl, cavity);
+  (void)hipStreamSynchronize(ps.c->stream);
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  bool mir = false; for (const EngProb& P : pl.probs) mir = mir || P.mirror;
+  fprintf(stderr, "[engine launch] nprob=%zu caps=%dx%d->%d ny=%d q=%d small=%d grid=%d mirror=%d cavity=%d  %10.1f ms\n", pl.probs.size(), pl.cap1, pl.cap2,
+          pl.capout, pl.ny, pl.q, (int)pl.small, (int)pl.ext, (int)mir, (int)cavity, ms);
+  return rc;
+}
+// One batched launch of a small kernel (256 threads per block, problem records at the head of the scratch arena).
+// `extra` bytes behind the records, from the next 256-byte boundary, belong to the caller, who lays them out in
+// `place(extra base)` before the copy.  The stream is drained before the return, so `probs` may die afterwards.
+struct NoExtra { void operator()(char*) const {} };
+template <class P, class Place = NoExtra>
+static int launch_batched(mpbp_ctx* c, void (*kernel)(const P*, int), dim3 grid, std::vector<P>& probs, size_t extra = 0, Place place = {}) {
+  if (probs.empty()) return MPBP_OK;
+  const size_t rec = sizeof(P) * probs.size();
+  RCCHK(ensure_arena(c, c->scratch, rec + extra + 4096));
+  place(c->scratch.base + ((rec + 255) & ~size_t(255)));
+  HIPCHK(c, hipMemcpyAsync(c->scratch.base, probs.data(), rec, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c->stream, (const P*)c->scratch.base, c->L);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MPBP_OK;
+}
+// env problems, each with its [L+1][bmax] rvec scratch behind the problem records
+struct EnvBatch {
+  std::vector<EnvProb> ev; std::vector<size_t> off; size_t rvd = 0;
+  void add(const EnvProb& P, size_t rv_doubles) { off.push_back(rvd); rvd += rv_doubles; ev.push_back(P); }
+  int run(mpbp_ctx* c) {
+    return launch_batched(c, env_kernel, dim3((unsigned)ev.size()), ev, sizeof(double) * rvd + 4096,
+                          [&](char* rv) { for (size_t s = 0; s < ev.size(); s++) ev[s].rvec = (double*)rv + off[s]; });
+  }
+};
+// The compression of one train against the identity (A2 = the constant 1, all bonds 1): mirror = 1 for the
+// finalisation's mpem2 |> compress!(:left), 0 for the damping's compress!(new + c old).
+static void add_ident_problem(EngLaunchPlan& pl, const mpbp_ctx* c, const DevTrain& in, const DevTrain& out, int ny, const double* pyy, int mirror) {
+  EngProb P{};
+  P.A1 = in.cores; P.bond1 = in.bonds; P.stride1 = in.stride; P.ny1 = ny;
+  P.A2 = c->d_one; P.bond2 = c->d_ones; P.stride2 = 0; P.ny2 = 1;
+  P.logz1 = in.logz; P.logz2 = nullptr;
+  P.pyy = pyy; P.pyy_tstride = 0;
+  P.ny = ny; P.q = 1; P.mirror = mirror; P.cap_out = c->cap;
+  P.out = out.cores; P.obond = out.bonds; P.ostride = out.stride; P.ologz = out.logz;
+  pl.probs.push_back(P); pl.cost.push_back((double)in.cap);
+  pl.cap1 = std::max(pl.cap1, in.cap);
+}
+// the launch plan of such compressions: trains of bond <= cap1 with ny states per time
+static EngLaunchPlan ident_plan(const Pass& ps, int cap1, int ny) {
+  EngLaunchPlan pl;
+  pl.q = 1; pl.capout = ps.c->cap; pl.cap1 = cap1; pl.cap2 = 1; pl.ny1 = ny; pl.ny2 = 1; pl.ny = ny;
+  pl.small = small_problem(ps.env, cap1, ny, 1);
+  return pl;
+}
+// One engine launch of the cavity products ops[ks] (a cavity launch of the 512-thread engine unless `small`).
+static int launch_ops(Pass& ps, const std::vector<OpRec>& ops, const std::vector<DevTrain>& tr, const std::vector<int>& ks, bool small) {
+  const mpbp_ctx* c = ps.c;
+  EngLaunchPlan pl; pl.q = c->q; pl.capout = c->cap; pl.small = small;
+  for (int k : ks) {
+    const OpRec& o = ops[k];
+    const NodeFactor& f = c->fac[o.node];
+    const DevTrain &a = tr[o.in1], &b = tr[o.in2], &out = tr[o.out];
+    EngProb P{};
+    P.A1 = a.cores; P.bond1 = a.bonds; P.stride1 = a.stride; P.ny1 = a.ny;
+    P.A2 = b.cores; P.bond2 = b.bonds; P.stride2 = b.stride; P.ny2 = b.ny;
+    P.logz1 = a.logz; P.logz2 = b.logz;
+    P.pyy = c->d_tab + c->pyy_base[o.node] + f.yy_off[o.d1 * (f.deg + 1) + o.d2];
+    P.pyy_tstride = f.nt == 1 ? 0 : f.yy_tblock;
+    P.ny = out.ny; P.q = c->q; P.mirror = 0; P.cap_out = c->cap;
+    P.out = out.cores; P.obond = out.bonds; P.ostride = out.stride; P.ologz = out.logz;
+    pl.probs.push_back(P);
+    const double B = (double)a.cap * b.cap;
+    pl.cost.push_back(B * B * B * out.ny);
+    pl.cap1 = std::max(pl.cap1, a.cap); pl.cap2 = std::max(pl.cap2, b.cap);
+    pl.ny1 = std::max(pl.ny1, a.ny); pl.ny2 = std::max(pl.ny2, b.ny); pl.ny = std::max(pl.ny, out.ny);
+  }
+  return launch_engine(ps, pl, !small);
+}
 // internal: the work trains of this node list do not fit the device - the caller splits the list
 #define MPBP_ESPLIT_INTERNAL (-1000)
 
-// One pass over `nodes` (validated by mpbp_sweep).  Reads the incoming messages from c->read_cores / read_bonds (the
-// live slab, or the snapshot taken by mpbp_sweep when a Jacobi sweep has to be split), writes the live slab.
-static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_trunc trunc, double damp, mpbp_stats* stats, bool may_split) {
-  const int L = c->L, q = c->q, cap = c->cap;
-  EventPair evs;
-  hipEvent_t ev0 = evs.a, ev1 = evs.b;
-  hipEventRecord(ev0, c->stream);
-  HIPCHK(c, hipMemsetAsync(c->d_stats, 0, sizeof(EngStats), c->stream));
-  float ms_orth = 0.f; int n_orth = 0;
-
-  // ---------------------------------------------------------------- plan: trains, ops, levels
-  struct TrainSpec { int cap, ny, qphys; int d; int level; int64_t tab_off; bool is_init; int node; int kron_skip = -2; };   // kron_skip >= -1: product of the node's in-messages except that position (generic factors)
-  std::vector<TrainSpec> specs;     // scratch trains to allocate
-  std::vector<DevTrain> tr;         // filled after allocation (same indexing)
-  auto new_train = [&](int capv, int ny, int qphys, int d, int level) {
-    specs.push_back({capv, ny, qphys, d, level, 0, false, -1});
+// ---------------------------------------------------------------- the stages of one pass
+// Plan (host only): the trains, the cavity ops with their levels, and the finalisation records of `nodes`.
+static int plan_sweep(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, double damp, SweepPlan& sp) {
+  const int q = c->q, cap = c->cap;
+  std::vector<TrainSpec>& specs = sp.specs;
+  auto new_train = [&](int capv, int ny, int qphys, int d, int level, int node = -1, int kron_skip = -2) {
+    specs.push_back({capv, ny, qphys, d, level, 0, false, node, kron_skip});
     return (int)specs.size() - 1;
   };
   // generic factors (mpbp_set_generic_factor): cap^n bond and q^n joint neighbour states of a product of n messages
   auto ipow = [](int64_t b, int n) { int64_t r = 1; for (int k = 0; k < n; k++) { r *= b; if (r > ((int64_t)1 << 40)) break; } return r; };
-  bool any_generic = false;
-  std::vector<OpRec> ops;
-  struct NodePlan { int node; std::vector<int> src, dest; int full; int init; };
-  std::vector<NodePlan> plans(n_nodes);
-  int maxlevel = 0;
+  sp.plans.resize(n_nodes);
   for (int k = 0; k < n_nodes; k++) {
     const int i = nodes[k];
     const NodeFactor& f = c->fac[i];
     const int z = f.deg;
-    NodePlan& P = plans[k];
+    NodePlan& P = sp.plans[k];
     P.node = i;
+    P.dest.assign(z, -1);
     if (f.generic) {
       // Exhaustive-trace update (reference src/bp_core.jl:18-93, src/mpbp.jl:117-154): no cavity; the message to neighbour j
       // sums over the joint states of the other z-1 neighbours, the belief over all z.  The mirrored engine compresses the
       // embeddings in one 512-thread workgroup each, whose register panel holds 2048 rows of Y_t.
-      any_generic = true;
+      sp.any_generic = true;
       const int64_t bm = ipow(cap, z - 1) * c->ct_factor(), bb = ipow(cap, z) * c->ct_factor();
       if (z > 0 && (bm * q * q > 2048 || bb * q > 2048))
         return c->fail(MPBP_EUNSUPPORTED, "node %d: generic factor of degree %d with max_bond %d needs product bonds %lld / %lld (limit: q^2 x bond <= 2048 rows); "
                        "the exhaustive update is exponential in the degree - use a RecursiveBPFactor model, a smaller max_bond or fewer neighbours",
                        i, z, cap, (long long)bm, (long long)bb);
       P.init = -1;
-      P.dest.assign(z, -1);
-      for (int j = 0; j < z; j++) {
-        P.dest[j] = new_train((int)ipow(cap, z - 1), (int)ipow(q, z - 1), q, 0, 0);
-        specs[P.dest[j]].node = i; specs[P.dest[j]].kron_skip = j;
-      }
-      P.full = new_train((int)ipow(cap, z), (int)ipow(q, z), q, 0, 0);
-      specs[P.full].node = i; specs[P.full].kron_skip = -1;
+      for (int j = 0; j < z; j++) P.dest[j] = new_train((int)ipow(cap, z - 1), (int)ipow(q, z - 1), q, 0, 0, i, j);
+      P.full = new_train((int)ipow(cap, z), (int)ipow(q, z), q, 0, 0, i, -1);
       continue;
     }
-    P.init = new_train(1, f.ny[0], q, 0, 0);
-    specs[P.init].is_init = true; specs[P.init].node = i;
+    P.init = new_train(1, f.ny[0], q, 0, 0, i);
+    specs[P.init].is_init = true;
     for (int j = 0; j < z; j++) P.src.push_back(new_train(cap, f.ny[1], q, 1, 0));
     auto op = [&](int a, int b) {
       const int d1 = specs[a].d, d2 = specs[b].d;
       const int lev = std::max(specs[a].level, specs[b].level) + 1;
       const int o = new_train(cap, f.ny[d1 + d2], q, d1 + d2, lev);
-      ops.push_back({a, b, o, d1, d2, i, lev});
-      maxlevel = std::max(maxlevel, lev);
+      sp.ops.push_back({a, b, o, d1, d2, i, lev});
+      sp.maxlevel = std::max(sp.maxlevel, lev);
       return o;
     };
     // CavityTools.cavity (3z-2 calls in this order)
-    P.dest.assign(z, -1);
     if (z == 0) P.full = P.init;
     else if (z == 1) { P.dest[0] = P.init; P.full = op(P.src[0], P.init); }
     else {
@@ -769,12 +850,9 @@ static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_
       P.dest[0] = right;
     }
   }
-  // finalisation trains: ctilde (bond 2*cap... = q*cap), engine output (message), belief ctilde
-  struct FinRec { int k, j, p, src, ct, out; int nrm = -1, sum = -1, out2 = -1, occ = 0; bool gen = false; };
-  std::vector<FinRec> fins; std::vector<FinRec> bels;
   const int capct = c->ct_factor() * cap;
   for (int k = 0; k < n_nodes; k++) {
-    NodePlan& P = plans[k];
+    NodePlan& P = sp.plans[k];
     const int i = P.node; const int z = c->fac[i].deg;
     const bool gen = c->fac[i].generic;
     for (int j = 0; j < z; j++) {
@@ -789,28 +867,24 @@ static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_
         fr.out2 = new_train(cap, q * q, 1, 0, 0);           // compressed again
         for (int j2 = 0; j2 < j; j2++) if (c->out_edge[c->nbr_ptr[i] + j2] == c->out_edge[p]) fr.occ++;
       }
-      fins.push_back(fr);
+      sp.fins.push_back(fr);
     }
     const int ctb = new_train(gen ? c->ct_factor() * specs[P.full].cap : capct, q, 1, 0, 0);           // belief: qj = 1
     FinRec br{k, -1, -1, P.full, ctb, -1};
     br.gen = gen;
     if (gen) br.out = new_train(cap, q, 1, 0, 0);           // the generic belief is compressed before it is marginalised (src/mpbp.jl:145-154)
-    bels.push_back(br);
+    sp.bels.push_back(br);
   }
-  // ---------------------------------------------------------------- allocate the arena
-  c->arena.reset();
+  return MPBP_OK;
+}
+// Allocate: every work train of the pass in c->arena (two passes: measure, grow, lay out).  Returns MPBP_ESPLIT_INTERNAL
+// when the node list should be split.
+static int allocate_trains(mpbp_ctx* c, const SweepPlan& sp, const SweepEnv& env, std::vector<DevTrain>& tr) {
+  const std::vector<TrainSpec>& specs = sp.specs;
+  const int L = c->L, n_nodes = (int)sp.plans.size();
   tr.resize(specs.size());
-  auto bytes_of = [&](const TrainSpec& s) {
-    int64_t stride = ((int64_t)s.cap * s.cap * s.ny * s.qphys + 3) & ~int64_t(3);
-    return std::pair<int64_t, int64_t>(stride, stride * L);
-  };
-  if (may_split && n_nodes > 1) {
-    // MPBP_DEBUG_SPLIT_NODES=k: take the split path whenever a pass lists more than k nodes (tests of the snapshot logic;
-    // read on every call so that a test can switch it)
-    const char* e = getenv("MPBP_DEBUG_SPLIT_NODES");
-    const int dbg_split = e ? atoi(e) : 0;
-    if (dbg_split > 0 && n_nodes > dbg_split) return MPBP_ESPLIT_INTERNAL;
-  }
+  // MPBP_DEBUG_SPLIT_NODES=k: take the split path whenever a pass lists more than k nodes (tests of the snapshot logic)
+  if (env.split_nodes > 0 && n_nodes > env.split_nodes) return MPBP_ESPLIT_INTERNAL;
   for (int pass = 0; pass < 2; pass++) {
     c->arena.reset();
     bool ok = true;
@@ -820,323 +894,226 @@ static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_
         // the init train (src/recursive_bp_factor.jl:133-138) is read straight from the table blob:
         // cores [1,1,ny0,q] per time = prob_y0, all bonds 1, z = 1
         const int i = specs[s].node;
-        tr[s].cores = c->d_tab + c->init_off[i]; tr[s].stride = (int64_t)c->fac[i].ny[0] * q;
+        tr[s].cores = c->d_tab + c->init_off[i]; tr[s].stride = (int64_t)c->fac[i].ny[0] * c->q;
         tr[s].bonds = c->d_ones; tr[s].logz = c->d_one + 1;
         continue;
       }
-      auto bs = bytes_of(specs[s]);
-      tr[s].stride = bs.first;
-      tr[s].cores = (double*)c->arena.take(sizeof(double) * bs.second);
+      const int64_t stride = ((int64_t)specs[s].cap * specs[s].cap * specs[s].ny * specs[s].qphys + 3) & ~int64_t(3);
+      tr[s].stride = stride;
+      tr[s].cores = (double*)c->arena.take(sizeof(double) * stride * L);
       tr[s].bonds = (int32_t*)c->arena.take(sizeof(int32_t) * (L + 2));
       tr[s].logz = (double*)c->arena.take(sizeof(double) * 2);
       if (!tr[s].cores || !tr[s].bonds || !tr[s].logz) ok = false;
     }
     if (ok) break;
     if (pass == 1) return c->fail(MPBP_ENOMEM, "work arena too small");
-    if (may_split && n_nodes > 1) {
+    if (n_nodes > 1) {
       // every work train of the pass is resident at once (config 3 on one GPU: 300 GB for the 2048 nodes): past 45 %
       // of what the context can get, the node list is split and the halves run one after the other
-      size_t freeb = 0, totb = 0;
-      hipMemGetInfo(&freeb, &totb);
-      const size_t reach = freeb + c->arena.cap + c->scratch.cap + c->v2arena.cap;
+      const size_t reach = free_bytes() + c->arena.cap + c->scratch.cap + c->v2arena.cap;
       if (c->arena.want > (size_t)(0.45 * (double)reach)) return MPBP_ESPLIT_INTERNAL;
     }
-    int rc = ensure_arena(c, c->arena, c->arena.want + (1 << 20));
-    if (rc != MPBP_OK) return rc;
+    RCCHK(ensure_arena(c, c->arena, c->arena.want + (1 << 20)));
   }
-  // ---------------------------------------------------------------- prep: sources from the messages
-  {
-    std::vector<PrepProb> pp;
-    for (int k = 0; k < n_nodes; k++) {
-      const int i = plans[k].node; const NodeFactor& f = c->fac[i];
-      if (f.generic) continue;
-      for (int j = 0; j < f.deg; j++) {
-        const int p = c->nbr_ptr[i] + j;
-        const int ein = c->in_edge[p];
-        DevTrain& o = tr[plans[k].src[j]];
-        PrepProb P{};
-        P.msg = c->read_slot_cores(ein); P.mbond = c->read_slot_bonds(ein); P.mstride = c->core_stride;
-        P.tab = c->d_tab + c->pxy_off[p]; P.tab_tstride = c->pxy_tstride[p];
-        P.out = o.cores; P.obond = o.bonds; P.ostride = o.stride; P.ologz = o.logz; P.ny1 = f.ny[1]; P.q = q;
-        pp.push_back(P);
-      }
-    }
-    if (!pp.empty()) {
-      int rc = ensure_arena(c, c->scratch, sizeof(PrepProb) * pp.size() + 4096);
-      if (rc != MPBP_OK) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->scratch.base, pp.data(), sizeof(PrepProb) * pp.size(), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(prep_kernel, dim3(L, (unsigned)pp.size()), dim3(256), 0, c->stream, (const PrepProb*)c->scratch.base, L);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
+  return MPBP_OK;
+}
+// prep: the source trains of the cavity from the incoming messages
+static int run_prep(mpbp_ctx* c, const SweepPlan& sp, const std::vector<DevTrain>& tr) {
+  std::vector<PrepProb> pp;
+  for (const NodePlan& np : sp.plans) {
+    const NodeFactor& f = c->fac[np.node];
+    if (f.generic) continue;
+    for (int j = 0; j < f.deg; j++) {
+      const int p = c->nbr_ptr[np.node] + j;
+      const int ein = c->in_edge[p];
+      const DevTrain& o = tr[np.src[j]];
+      PrepProb P{};
+      P.msg = c->read_slot_cores(ein); P.mbond = c->read_slot_bonds(ein); P.mstride = c->core_stride;
+      P.tab = c->d_tab + c->pxy_off[p]; P.tab_tstride = c->pxy_tstride[p];
+      P.out = o.cores; P.obond = o.bonds; P.ostride = o.stride; P.ologz = o.logz; P.ny1 = f.ny[1]; P.q = c->q;
+      pp.push_back(P);
     }
   }
-  // ---------------------------------------------------------------- generic factors: products of the in-messages
-  if (any_generic) {
-    std::vector<KronProb> kp;
-    for (size_t s2 = 0; s2 < specs.size(); s2++) {
-      if (specs[s2].kron_skip < -1) continue;
-      const int i = specs[s2].node;
-      KronProb K{};
-      K.nk = 0; K.q = q; K.mstride = c->core_stride;
-      for (int j = 0; j < c->fac[i].deg; j++) {
-        if (j == specs[s2].kron_skip) continue;
-        const int ein = c->in_edge[c->nbr_ptr[i] + j];
-        K.msg[K.nk] = c->read_slot_cores(ein); K.mbond[K.nk] = c->read_slot_bonds(ein); K.nk++;
-      }
-      K.out = tr[s2].cores; K.obond = tr[s2].bonds; K.ostride = tr[s2].stride; K.ologz = tr[s2].logz;
-      kp.push_back(K);
+  return launch_batched(c, prep_kernel, dim3(c->L, (unsigned)pp.size()), pp);
+}
+// generic factors: products of the in-messages
+static int run_kron(mpbp_ctx* c, const SweepPlan& sp, const std::vector<DevTrain>& tr) {
+  std::vector<KronProb> kp;
+  for (size_t s2 = 0; s2 < sp.specs.size(); s2++) {
+    if (sp.specs[s2].kron_skip < -1) continue;
+    const int i = sp.specs[s2].node;
+    KronProb K{};
+    K.nk = 0; K.q = c->q; K.mstride = c->core_stride;
+    for (int j = 0; j < c->fac[i].deg; j++) {
+      if (j == sp.specs[s2].kron_skip) continue;
+      const int ein = c->in_edge[c->nbr_ptr[i] + j];
+      K.msg[K.nk] = c->read_slot_cores(ein); K.mbond[K.nk] = c->read_slot_bonds(ein); K.nk++;
     }
-    int rc = ensure_arena(c, c->scratch, sizeof(KronProb) * kp.size() + 4096);
-    if (rc != MPBP_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->scratch.base, kp.data(), sizeof(KronProb) * kp.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(kron_kernel, dim3(L, (unsigned)kp.size()), dim3(256), 0, c->stream, (const KronProb*)c->scratch.base, L);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    K.out = tr[s2].cores; K.obond = tr[s2].bonds; K.ostride = tr[s2].stride; K.ologz = tr[s2].logz;
+    kp.push_back(K);
   }
-  // ---------------------------------------------------------------- cavity ops
-  // The single-wave problems go level by level.  The 512-thread problems are packed into launches by readiness
-  // rather than by level: a launch takes the problems whose inputs exist, cut to a whole number of rounds of the
-  // resident workgroups when more are ready (problems that others wait for first), so that a rank with few nodes
-  // (128 nodes: 128 + 384 problems in two levels) fills the CUs in 2 rounds instead of 1 + 2 half-empty ones.
-  // This needs the 512-thread problems to read single-wave results of level 1 only (products with the bond-1
-  // initial train) - checked, with the plain level-by-level order as the fallback.
-  {
-    auto is_small = [&](const OpRec& o) { return small_problem((int64_t)tr[o.in1].cap * tr[o.in2].cap, tr[o.out].ny, q); };
-    std::vector<char> train_small(specs.size(), 0), avail(specs.size(), 1);
-    std::vector<int> train_level(specs.size(), 0);
-    bool pack_ok = getenv("MPBP_DEBUG_NO_PACK") == nullptr;
-    for (const OpRec& o : ops) { train_small[o.out] = is_small(o) ? 1 : 0; train_level[o.out] = o.level; avail[o.out] = 0; }
-    for (const OpRec& o : ops)
-      if (!is_small(o))
-        for (int in : {o.in1, o.in2})
-          if (train_level[in] > 1 && train_small[in]) pack_ok = false;
-    auto add_problem = [&](EngLaunchPlan& pl, const OpRec& o) {
-      const NodeFactor& f = c->fac[o.node];
-      const DevTrain &a = tr[o.in1], &b = tr[o.in2], &out = tr[o.out];
-      EngProb P{};
-      P.A1 = a.cores; P.bond1 = a.bonds; P.stride1 = a.stride; P.ny1 = a.ny;
-      P.A2 = b.cores; P.bond2 = b.bonds; P.stride2 = b.stride; P.ny2 = b.ny;
-      P.logz1 = a.logz; P.logz2 = b.logz;
-      P.pyy = c->d_tab + c->pyy_base[o.node] + f.yy_off[o.d1 * (f.deg + 1) + o.d2];
-      P.pyy_tstride = f.nt == 1 ? 0 : f.yy_tblock;
-      P.ny = out.ny; P.q = q; P.mirror = 0; P.cap_out = cap;
-      P.out = out.cores; P.obond = out.bonds; P.ostride = out.stride; P.ologz = out.logz;
-      pl.probs.push_back(P);
-      const double B = (double)a.cap * b.cap;
-      pl.cost.push_back(B * B * B * out.ny);
-      pl.cap1 = std::max(pl.cap1, a.cap); pl.cap2 = std::max(pl.cap2, b.cap);
-      pl.ny1 = std::max(pl.ny1, a.ny); pl.ny2 = std::max(pl.ny2, b.ny); pl.ny = std::max(pl.ny, out.ny);
-    };
-    auto small_level = [&](int lev) -> int {
-      EngLaunchPlan pls; pls.q = q; pls.capout = cap; pls.small = true;
-      for (const OpRec& o : ops) if (o.level == lev && is_small(o)) { add_problem(pls, o); avail[o.out] = 1; }
-      return launch_engine(c, pls, trunc, false, &ms_orth, &n_orth);
-    };
-    if (pack_ok) {
-      int rc = small_level(1);
-      if (rc != MPBP_OK) return rc;
-      std::vector<int> rem;                       // indices into ops of the 512-thread problems not launched yet
-      for (int k = 0; k < (int)ops.size(); k++) if (!is_small(ops[k])) rem.push_back(k);
-      std::vector<char> needed(specs.size(), 0);  // trains some remaining 512-thread problem reads
-      const int round = std::max(1, c->num_cu);
-      while (!rem.empty()) {
-        std::vector<int> ready, later;
-        for (int k : rem) (avail[ops[k].in1] && avail[ops[k].in2] ? ready : later).push_back(k);
-        if (ready.empty()) return c->fail(MPBP_EINVAL, "internal: cavity dependency graph is not acyclic");
-        if ((int)ready.size() > round && !later.empty()) {
-          std::fill(needed.begin(), needed.end(), 0);
-          for (int k : later) { needed[ops[k].in1] = 1; needed[ops[k].in2] = 1; }
-          std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return needed[ops[a].out] > needed[ops[b].out]; });
-          const size_t take = (ready.size() / round) * round;
-          later.insert(later.end(), ready.begin() + take, ready.end());
-          ready.resize(take);
-        }
-        EngLaunchPlan plb; plb.q = q; plb.capout = cap;
-        for (int k : ready) add_problem(plb, ops[k]);
-        rc = launch_engine(c, plb, trunc, true, &ms_orth, &n_orth);
-        if (rc != MPBP_OK) return rc;
-        for (int k : ready) avail[ops[k].out] = 1;
-        rem.swap(later);
-      }
-      // the single-wave problems above level 1 (products with the bond-1 init train: dest[z-1], full): by readiness as well -
-      // everything they read exists by now, so they share ONE launch instead of one per level (each launch is a sequential
-      // chain of T + 1 time steps: configs[4] 0.75 s, configs[3] ~0.3 s per level)
-      std::vector<int> srem;
-      for (int k = 0; k < (int)ops.size(); k++) if (is_small(ops[k]) && ops[k].level >= 2) srem.push_back(k);
-      while (!srem.empty()) {
-        std::vector<int> ready, later;
-        for (int k : srem) (avail[ops[k].in1] && avail[ops[k].in2] ? ready : later).push_back(k);
-        if (ready.empty()) return c->fail(MPBP_EINVAL, "internal: cavity dependency graph is not acyclic");
-        EngLaunchPlan pls; pls.q = q; pls.capout = cap; pls.small = true;
-        for (int k : ready) add_problem(pls, ops[k]);
-        rc = launch_engine(c, pls, trunc, false, &ms_orth, &n_orth);
-        if (rc != MPBP_OK) return rc;
-        for (int k : ready) avail[ops[k].out] = 1;
-        srem.swap(later);
-      }
-    } else {
-      for (int lev = 1; lev <= maxlevel; lev++) {
-        EngLaunchPlan plb; plb.q = q; plb.capout = cap;
-        for (const OpRec& o : ops) if (o.level == lev && !is_small(o)) add_problem(plb, o);
-        int rc = launch_engine(c, plb, trunc, true, &ms_orth, &n_orth);
-        if (rc != MPBP_OK) return rc;
-        rc = small_level(lev);
-        if (rc != MPBP_OK) return rc;
-      }
+  return launch_batched(c, kron_kernel, dim3(c->L, (unsigned)kp.size()), kp);
+}
+// Launches the cavity ops `rem` (indices into ops) by readiness: each launch takes the ops whose inputs exist.  On the
+// 512-thread engine (small = false) a launch is cut to a whole number of rounds of the resident workgroups when more
+// are ready, the ops that others wait for first.
+static int launch_by_readiness(Pass& ps, const std::vector<OpRec>& ops, const std::vector<DevTrain>& tr, std::vector<int> rem, std::vector<char>& avail, bool small) {
+  mpbp_ctx* c = ps.c;
+  std::vector<char> needed(tr.size(), 0);     // trains some remaining problem reads
+  const int round = std::max(1, c->num_cu);
+  while (!rem.empty()) {
+    std::vector<int> ready, later;
+    for (int k : rem) (avail[ops[k].in1] && avail[ops[k].in2] ? ready : later).push_back(k);
+    if (ready.empty()) return c->fail(MPBP_EINVAL, "internal: cavity dependency graph is not acyclic");
+    if (!small && (int)ready.size() > round && !later.empty()) {
+      std::fill(needed.begin(), needed.end(), 0);
+      for (int k : later) { needed[ops[k].in1] = 1; needed[ops[k].in2] = 1; }
+      std::stable_sort(ready.begin(), ready.end(), [&](int a, int b) { return needed[ops[a].out] > needed[ops[b].out]; });
+      const size_t take = (ready.size() / round) * round;
+      later.insert(later.end(), ready.begin() + take, ready.end());
+      ready.resize(take);
     }
+    RCCHK(launch_ops(ps, ops, tr, ready, small));
+    for (int k : ready) avail[ops[k].out] = 1;
+    rem.swap(later);
   }
-  // ---------------------------------------------------------------- finalise messages + beliefs
-  {
-    std::vector<CtProb> cps;
-    for (const FinRec& fr : fins) {
-      const int i = plans[fr.k].node; const NodeFactor& f = c->fac[i];
-      const DevTrain &s = tr[fr.src], &ct = tr[fr.ct];
-      CtProb P{};
-      P.in = s.cores; P.ibond = s.bonds; P.istride = s.stride; P.ilogz = s.logz; P.ny = s.ny;
-      P.W = c->d_tab + c->wmsg_off[fr.p]; P.q = q; P.qj = q; P.periodic = c->periodic ? 1 : 0;
-      P.out = ct.cores; P.obond = ct.bonds; P.ostride = ct.stride; P.ologz = ct.logz;
-      (void)f;
-      cps.push_back(P);
+  return MPBP_OK;
+}
+// The cavity ops.  The single-wave problems go level by level.  The 512-thread problems are packed into launches by
+// readiness rather than by level: a launch takes the problems whose inputs exist, cut to a whole number of rounds of the
+// resident workgroups when more are ready (problems that others wait for first), so that a rank with few nodes
+// (128 nodes: 128 + 384 problems in two levels) fills the CUs in 2 rounds instead of 1 + 2 half-empty ones.
+// This needs the 512-thread problems to read single-wave results of level 1 only (products with the bond-1
+// initial train) - checked, with the plain level-by-level order as the fallback.
+static int run_cavity(Pass& ps, const SweepPlan& sp, const std::vector<DevTrain>& tr) {
+  const std::vector<OpRec>& ops = sp.ops;
+  auto is_small = [&](const OpRec& o) { return small_problem(ps.env, (int64_t)tr[o.in1].cap * tr[o.in2].cap, tr[o.out].ny, ps.c->q); };
+  std::vector<char> train_small(tr.size(), 0), avail(tr.size(), 1);
+  std::vector<int> train_level(tr.size(), 0);
+  bool pack_ok = !ps.env.no_pack;
+  for (const OpRec& o : ops) { train_small[o.out] = is_small(o) ? 1 : 0; train_level[o.out] = o.level; avail[o.out] = 0; }
+  for (const OpRec& o : ops)
+    if (!is_small(o))
+      for (int in : {o.in1, o.in2})
+        if (train_level[in] > 1 && train_small[in]) pack_ok = false;
+  auto level = [&](int lev, bool small) {      // the ops of one level on one engine variant
+    std::vector<int> ks;
+    for (int k = 0; k < (int)ops.size(); k++) if (ops[k].level == lev && is_small(ops[k]) == small) { ks.push_back(k); avail[ops[k].out] = 1; }
+    return ks;
+  };
+  if (!pack_ok) {
+    for (int lev = 1; lev <= sp.maxlevel; lev++) {
+      RCCHK(launch_ops(ps, ops, tr, level(lev, false), false));
+      RCCHK(launch_ops(ps, ops, tr, level(lev, true), true));
     }
-    for (const FinRec& fr : bels) {
-      const int i = plans[fr.k].node;
-      const DevTrain &s = tr[fr.src], &ct = tr[fr.ct];
-      CtProb P{};
-      P.in = s.cores; P.ibond = s.bonds; P.istride = s.stride; P.ilogz = s.logz; P.ny = s.ny;
-      P.W = c->d_tab + c->wbel_off[i]; P.q = q; P.qj = 1; P.periodic = c->periodic ? 1 : 0;
-      P.out = ct.cores; P.obond = ct.bonds; P.ostride = ct.stride; P.ologz = ct.logz;
-      cps.push_back(P);
-    }
-    if (!cps.empty()) {
-      int rc = ensure_arena(c, c->scratch, sizeof(CtProb) * cps.size() + 4096);
-      if (rc != MPBP_OK) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->scratch.base, cps.data(), sizeof(CtProb) * cps.size(), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(ctilde_kernel, dim3(L, (unsigned)cps.size()), dim3(256), 0, c->stream, (const CtProb*)c->scratch.base, L);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    // engine (mirror): mpem2 |> compress!(:left) |> normalize_eachmatrix!
-    EngLaunchPlan pl; pl.q = 1; pl.capout = cap; pl.cap1 = capct; pl.cap2 = 1; pl.ny1 = q * q; pl.ny2 = 1; pl.ny = q * q;
-    pl.small = small_problem(capct, q * q, 1);
-    // generic factors: embeddings of bond q cap^(z-1) (messages, ny = q qj) and q cap^z (beliefs, ny = q), own launches
-    EngLaunchPlan plg = pl, plgb = pl;
-    plg.cap1 = 1; plgb.cap1 = 1; plgb.ny1 = q; plgb.ny = q;
-    auto mirror_problem = [&](EngLaunchPlan& plan, const FinRec& fr, int nyv, const double* ident) {
-      const DevTrain &ct = tr[fr.ct], &out = tr[fr.out];
-      EngProb P{};
-      P.A1 = ct.cores; P.bond1 = ct.bonds; P.stride1 = ct.stride; P.ny1 = nyv;
-      P.A2 = c->d_one; P.bond2 = c->d_ones; P.stride2 = 0; P.ny2 = 1;
-      P.logz1 = ct.logz; P.logz2 = nullptr;
-      P.pyy = ident; P.pyy_tstride = 0;
-      P.ny = nyv; P.q = 1; P.mirror = 1; P.cap_out = cap;
-      P.out = out.cores; P.obond = out.bonds; P.ostride = out.stride; P.ologz = out.logz;
-      plan.probs.push_back(P); plan.cost.push_back((double)ct.cap);
-      plan.cap1 = std::max(plan.cap1, ct.cap);
-    };
-    for (const FinRec& fr : fins) mirror_problem(fr.gen ? plg : pl, fr, q * q, c->d_ident);
-    for (const FinRec& fr : bels) if (fr.gen) mirror_problem(plgb, fr, q, c->d_ident + (size_t)c->ident_n * c->ident_n);
-    int rc = launch_engine(c, pl, trunc, false, &ms_orth, &n_orth);
-    if (rc != MPBP_OK) return rc;
-    for (EngLaunchPlan* pg : {&plg, &plgb}) {
-      if (pg->probs.empty()) continue;
-      pg->small = small_problem(pg->cap1, pg->ny, 1);
-      rc = launch_engine(c, *pg, trunc, false, &ms_orth, &n_orth);
-      if (rc != MPBP_OK) return rc;
-    }
-    // env: normalize! the messages into the slab (damp = 0) or into a temporary (damp > 0);
-    //      beliefs marginals + log z_i
-    std::vector<EnvProb> eps;
-    size_t rv_doubles = 0;
-    std::vector<size_t> rv_off;
-    for (const FinRec& fr : fins) {
-      const int i = plans[fr.k].node; const int z = c->fac[i].deg;
+    return MPBP_OK;
+  }
+  RCCHK(launch_ops(ps, ops, tr, level(1, true), true));
+  std::vector<int> rem, srem;        // indices into ops of the 512-thread / single-wave problems not launched yet
+  for (int k = 0; k < (int)ops.size(); k++) {
+    if (!is_small(ops[k])) rem.push_back(k);
+    else if (ops[k].level >= 2) srem.push_back(k);
+  }
+  RCCHK(launch_by_readiness(ps, ops, tr, std::move(rem), avail, false));
+  // the single-wave problems above level 1 (products with the bond-1 init train: dest[z-1], full): by readiness as well -
+  // everything they read exists by now, so they share ONE launch instead of one per level (each launch is a sequential
+  // chain of T + 1 time steps: configs[4] 0.75 s, configs[3] ~0.3 s per level)
+  return launch_by_readiness(ps, ops, tr, std::move(srem), avail, true);
+}
+// ---- damping (reference src/recursive_bp_factor.jl:172-176): mu = compress!(new + damp/(1-damp) old), normalize!
+static int damp_messages(Pass& ps, const SweepPlan& sp, const std::vector<DevTrain>& tr) {
+  mpbp_ctx* c = ps.c;
+  const int L = c->L, q = c->q, cap = c->cap;
+  int maxocc = 0;
+  for (const FinRec& fr : sp.fins) if (!fr.gen) maxocc = std::max(maxocc, fr.occ);
+  for (int round = 0; round <= maxocc; round++) {      // aliased out-edges compound in the reference's loop order
+    std::vector<ComposeProb> cps; EngLaunchPlan pl = ident_plan(ps, 2 * cap, q * q); EnvBatch env;
+    for (const FinRec& fr : sp.fins) {
+      if (fr.occ != round || fr.gen) continue;
       const int eo = c->out_edge[fr.p];
-      // last occurrence of an aliased out-edge wins (reference src/recursive_bp_factor.jl:154-159)
-      bool last = true;
-      for (int j2 = fr.j + 1; j2 < z; j2++) if (c->out_edge[c->nbr_ptr[i] + j2] == eo) last = false;
-      const DevTrain& out = tr[fr.out];
-      EnvProb P{};
-      P.in = out.cores; P.ibond = out.bonds; P.istride = out.stride; P.ilogz = out.logz; P.p = q * q;
-      if (damp > 0.0 && !fr.gen) { const DevTrain& nm = tr[fr.nrm]; P.dst = nm.cores; P.dbond = nm.bonds; P.dstride = nm.stride; }
-      else { P.dst = last ? c->slot_cores(eo) : nullptr; P.dbond = last ? c->slot_bonds(eo) : nullptr; P.dstride = c->core_stride; }
-      P.marg = nullptr; P.logz_out = c->d_logz_pos + fr.p; P.bmax = cap;
-      rv_off.push_back(rv_doubles); rv_doubles += (size_t)(L + 1) * cap;
-      eps.push_back(P);
+      const DevTrain &nm = tr[fr.nrm], &sm = tr[fr.sum], &o2 = tr[fr.out2];
+      ComposeProb CP{};
+      CP.an = nm.cores; CP.bn = nm.bonds; CP.nstride = nm.stride;
+      CP.ao = c->slot_cores(eo); CP.bo = c->slot_bonds(eo); CP.ostride = c->core_stride;
+      CP.out = sm.cores; CP.obond = sm.bonds; CP.outstride = sm.stride; CP.ologz = sm.logz;
+      CP.c = ps.damp / (1.0 - ps.damp); CP.p = q * q;
+      cps.push_back(CP);
+      add_ident_problem(pl, c, sm, o2, q * q, c->d_ident, 0);
+      EnvProb VP{};
+      VP.in = o2.cores; VP.ibond = o2.bonds; VP.istride = o2.stride; VP.ilogz = o2.logz; VP.p = q * q;
+      VP.dst = c->slot_cores(eo); VP.dbond = c->slot_bonds(eo); VP.dstride = c->core_stride;
+      VP.marg = nullptr; VP.logz_out = nullptr; VP.bmax = cap;
+      env.add(VP, (size_t)(L + 1) * cap);
     }
-    for (const FinRec& fr : bels) {
-      const int i = plans[fr.k].node;
-      const DevTrain& ct = fr.gen ? tr[fr.out] : tr[fr.ct];
-      EnvProb P{};
-      P.in = ct.cores; P.ibond = ct.bonds; P.istride = ct.stride; P.ilogz = ct.logz; P.p = q;
-      P.dst = c->d_btrain ? c->d_btrain + (int64_t)i * c->bt_slot : nullptr;
-      P.dbond = c->d_btrain ? c->d_bbond + (int64_t)i * (L + 1) : nullptr; P.dstride = c->bt_stride;
-      P.marg = c->d_beliefs + (size_t)q * L * i; P.logz_out = c->d_logz_node + i; P.bmax = fr.gen ? cap : capct;
-      rv_off.push_back(rv_doubles); rv_doubles += (size_t)(L + 1) * capct;
-      eps.push_back(P);
-    }
-    if (capct > 256) return c->fail(MPBP_EUNSUPPORTED, "q*max_bond (q*q*max_bond for periodic chains) > 256 not supported by the scan kernels yet");
-    auto run_env = [&](std::vector<EnvProb>& ev, const std::vector<size_t>& off, size_t rvd) -> int {
-      if (ev.empty()) return MPBP_OK;
-      int rc2 = ensure_arena(c, c->scratch, sizeof(EnvProb) * ev.size() + sizeof(double) * rvd + 8192);
-      if (rc2 != MPBP_OK) return rc2;
-      double* rvbase = (double*)(c->scratch.base + ((sizeof(EnvProb) * ev.size() + 255) & ~size_t(255)));
-      for (size_t s2 = 0; s2 < ev.size(); s2++) ev[s2].rvec = rvbase + off[s2];
-      HIPCHK(c, hipMemcpyAsync(c->scratch.base, ev.data(), sizeof(EnvProb) * ev.size(), hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(env_kernel, dim3((unsigned)ev.size()), dim3(256), 0, c->stream, (const EnvProb*)c->scratch.base, L);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      return MPBP_OK;
-    };
-    rc = run_env(eps, rv_off, rv_doubles);
-    if (rc != MPBP_OK) return rc;
-    // ---- damping (reference src/recursive_bp_factor.jl:172-176): mu = compress!(new + damp/(1-damp) old), normalize!
-    if (damp > 0.0) {
-      int maxocc = 0;
-      for (const FinRec& fr : fins) if (!fr.gen) maxocc = std::max(maxocc, fr.occ);
-      for (int round = 0; round <= maxocc; round++) {      // aliased out-edges compound in the reference's loop order
-        std::vector<ComposeProb> cps2; EngLaunchPlan pl2; std::vector<EnvProb> ev2; std::vector<size_t> off2; size_t rvd2 = 0;
-        pl2.q = 1; pl2.capout = cap; pl2.cap1 = 2 * cap; pl2.cap2 = 1; pl2.ny1 = q * q; pl2.ny2 = 1; pl2.ny = q * q;
-        pl2.small = small_problem(2 * cap, q * q, 1);
-        for (const FinRec& fr : fins) {
-          if (fr.occ != round || fr.gen) continue;
-          const int eo = c->out_edge[fr.p];
-          const DevTrain &nm = tr[fr.nrm], &sm = tr[fr.sum], &o2 = tr[fr.out2];
-          ComposeProb CP{};
-          CP.an = nm.cores; CP.bn = nm.bonds; CP.nstride = nm.stride;
-          CP.ao = c->slot_cores(eo); CP.bo = c->slot_bonds(eo); CP.ostride = c->core_stride;
-          CP.out = sm.cores; CP.obond = sm.bonds; CP.outstride = sm.stride; CP.ologz = sm.logz;
-          CP.c = damp / (1.0 - damp); CP.p = q * q;
-          cps2.push_back(CP);
-          EngProb EP{};
-          EP.A1 = sm.cores; EP.bond1 = sm.bonds; EP.stride1 = sm.stride; EP.ny1 = q * q;
-          EP.A2 = c->d_one; EP.bond2 = c->d_ones; EP.stride2 = 0; EP.ny2 = 1;
-          EP.logz1 = sm.logz; EP.logz2 = nullptr; EP.pyy = c->d_ident; EP.pyy_tstride = 0;
-          EP.ny = q * q; EP.q = 1; EP.mirror = 0; EP.cap_out = cap;
-          EP.out = o2.cores; EP.obond = o2.bonds; EP.ostride = o2.stride; EP.ologz = o2.logz;
-          pl2.probs.push_back(EP); pl2.cost.push_back(1.0);
-          EnvProb VP{};
-          VP.in = o2.cores; VP.ibond = o2.bonds; VP.istride = o2.stride; VP.ilogz = o2.logz; VP.p = q * q;
-          VP.dst = c->slot_cores(eo); VP.dbond = c->slot_bonds(eo); VP.dstride = c->core_stride;
-          VP.marg = nullptr; VP.logz_out = nullptr; VP.bmax = cap;
-          off2.push_back(rvd2); rvd2 += (size_t)(L + 1) * cap;
-          ev2.push_back(VP);
-        }
-        if (cps2.empty()) continue;
-        rc = ensure_arena(c, c->scratch, sizeof(ComposeProb) * cps2.size() + 4096);
-        if (rc != MPBP_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->scratch.base, cps2.data(), sizeof(ComposeProb) * cps2.size(), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(compose_kernel, dim3(L, (unsigned)cps2.size()), dim3(256), 0, c->stream, (const ComposeProb*)c->scratch.base, L);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        rc = launch_engine(c, pl2, trunc, false, &ms_orth, &n_orth);
-        if (rc != MPBP_OK) return rc;
-        rc = run_env(ev2, off2, rvd2);
-        if (rc != MPBP_OK) return rc;
-      }
-    }
+    if (cps.empty()) continue;
+    RCCHK(launch_batched(c, compose_kernel, dim3(L, (unsigned)cps.size()), cps));
+    RCCHK(launch_engine(ps, pl, false));
+    RCCHK(env.run(c));
   }
-  // ---------------------------------------------------------------- f[i] (src/recursive_bp_factor.jl:163)
-  hipEventRecord(ev1, c->stream);
+  return MPBP_OK;
+}
+// Finalise messages + beliefs: ctilde, compression, normalize! (and damping).
+static int finalise(Pass& ps, const SweepPlan& sp, const std::vector<DevTrain>& tr) {
+  mpbp_ctx* c = ps.c;
+  const int L = c->L, q = c->q, cap = c->cap, capct = c->ct_factor() * cap;
+  std::vector<CtProb> cps;
+  auto add_ctilde = [&](const FinRec& fr, const double* W, int qj) {
+    const DevTrain &s = tr[fr.src], &ct = tr[fr.ct];
+    CtProb P{};
+    P.in = s.cores; P.ibond = s.bonds; P.istride = s.stride; P.ilogz = s.logz; P.ny = s.ny;
+    P.W = W; P.q = q; P.qj = qj; P.periodic = c->periodic ? 1 : 0;
+    P.out = ct.cores; P.obond = ct.bonds; P.ostride = ct.stride; P.ologz = ct.logz;
+    cps.push_back(P);
+  };
+  for (const FinRec& fr : sp.fins) add_ctilde(fr, c->d_tab + c->wmsg_off[fr.p], q);
+  for (const FinRec& fr : sp.bels) add_ctilde(fr, c->d_tab + c->wbel_off[sp.plans[fr.k].node], 1);
+  RCCHK(launch_batched(c, ctilde_kernel, dim3(L, (unsigned)cps.size()), cps));
+  // engine (mirror): mpem2 |> compress!(:left) |> normalize_eachmatrix!
+  // generic factors: embeddings of bond q cap^(z-1) (messages, ny = q qj) and q cap^z (beliefs, ny = q), own launches
+  EngLaunchPlan pl = ident_plan(ps, capct, q * q), plg = ident_plan(ps, 1, q * q), plgb = ident_plan(ps, 1, q);
+  for (const FinRec& fr : sp.fins) add_ident_problem(fr.gen ? plg : pl, c, tr[fr.ct], tr[fr.out], q * q, c->d_ident, 1);
+  for (const FinRec& fr : sp.bels) if (fr.gen) add_ident_problem(plgb, c, tr[fr.ct], tr[fr.out], q, c->d_ident + (size_t)c->ident_n * c->ident_n, 1);
+  RCCHK(launch_engine(ps, pl, false));
+  for (EngLaunchPlan* pg : {&plg, &plgb}) {
+    if (pg->probs.empty()) continue;
+    pg->small = small_problem(ps.env, pg->cap1, pg->ny, 1);
+    RCCHK(launch_engine(ps, *pg, false));
+  }
+  // env: normalize! the messages into the slab (damp = 0) or into a temporary (damp > 0);
+  //      beliefs marginals + log z_i
+  EnvBatch env;
+  for (const FinRec& fr : sp.fins) {
+    const int i = sp.plans[fr.k].node; const int z = c->fac[i].deg;
+    const int eo = c->out_edge[fr.p];
+    // last occurrence of an aliased out-edge wins (reference src/recursive_bp_factor.jl:154-159)
+    bool last = true;
+    for (int j2 = fr.j + 1; j2 < z; j2++) if (c->out_edge[c->nbr_ptr[i] + j2] == eo) last = false;
+    const DevTrain& out = tr[fr.out];
+    EnvProb P{};
+    P.in = out.cores; P.ibond = out.bonds; P.istride = out.stride; P.ilogz = out.logz; P.p = q * q;
+    if (ps.damp > 0.0 && !fr.gen) { const DevTrain& nm = tr[fr.nrm]; P.dst = nm.cores; P.dbond = nm.bonds; P.dstride = nm.stride; }
+    else { P.dst = last ? c->slot_cores(eo) : nullptr; P.dbond = last ? c->slot_bonds(eo) : nullptr; P.dstride = c->core_stride; }
+    P.marg = nullptr; P.logz_out = c->d_logz_pos + fr.p; P.bmax = cap;
+    env.add(P, (size_t)(L + 1) * cap);
+  }
+  for (const FinRec& fr : sp.bels) {
+    const int i = sp.plans[fr.k].node;
+    const DevTrain& ct = fr.gen ? tr[fr.out] : tr[fr.ct];
+    EnvProb P{};
+    P.in = ct.cores; P.ibond = ct.bonds; P.istride = ct.stride; P.ilogz = ct.logz; P.p = q;
+    P.dst = c->d_btrain ? c->d_btrain + (int64_t)i * c->bt_slot : nullptr;
+    P.dbond = c->d_btrain ? c->d_bbond + (int64_t)i * (L + 1) : nullptr; P.dstride = c->bt_stride;
+    P.marg = c->d_beliefs + (size_t)q * L * i; P.logz_out = c->d_logz_node + i; P.bmax = fr.gen ? cap : capct;
+    env.add(P, (size_t)(L + 1) * capct);
+  }
+  if (capct > 256) return c->fail(MPBP_EUNSUPPORTED, "q*max_bond (q*q*max_bond for periodic chains) > 256 not supported by the scan kernels yet");
+  RCCHK(env.run(c));
+  return ps.damp > 0.0 ? damp_messages(ps, sp, tr) : MPBP_OK;
+}
+// Epilogue: f[i] of the listed nodes (src/recursive_bp_factor.jl:163) and the statistics of the pass.
+static int read_back(Pass& ps, const int32_t* nodes, int32_t n_nodes, const EventPair& evs, mpbp_stats* stats) {
+  mpbp_ctx* c = ps.c;
+  hipEventRecord(evs.b, c->stream);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->h_logz_node.data(), c->d_logz_node, sizeof(double) * c->N, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(c->h_logz_pos.data(), c->d_logz_pos, sizeof(double) * c->nnz(), hipMemcpyDeviceToHost));
@@ -1148,17 +1125,33 @@ static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_
   }
   EngStats hs;
   HIPCHK(c, hipMemcpy(&hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost));
-  float ms = 0; hipEventElapsedTime(&ms, ev0, ev1);
+  float ms = 0; hipEventElapsedTime(&ms, evs.a, evs.b);
   mpbp_stats st{};
   { double v; unsigned long long b = hs.maxerr_bits; memcpy(&v, &b, 8); st.maxerr = v; }
   st.n_compress = (int64_t)hs.n_compress; st.nan_flag = hs.nan_flag; st.capacity_flag = hs.capacity_flag;
-  st.jacobi_not_converged = hs.jacobi_fail; st.jacobi_sweeps = (int64_t)hs.jac_sweeps; st.jacobi_calls = (int64_t)hs.jac_calls; st.ms_total = ms; st.ms_orth = ms_orth; st.n_orth_launches = n_orth;
+  st.jacobi_not_converged = hs.jacobi_fail; st.jacobi_sweeps = (int64_t)hs.jac_sweeps; st.jacobi_calls = (int64_t)hs.jac_calls; st.ms_total = ms; st.ms_orth = ps.ms_orth; st.n_orth_launches = ps.n_orth;
   c->last = st;
   if (stats) *stats = st;
-  if (hs.capacity_flag) return c->fail(MPBP_ECAPACITY, "a truncated bond exceeded max_bond=%d; results were clamped", cap);
+  if (hs.capacity_flag) return c->fail(MPBP_ECAPACITY, "a truncated bond exceeded max_bond=%d; results were clamped", c->cap);
   return MPBP_OK;
 }
-
+// One pass over `nodes` (validated by mpbp_sweep).  Reads the incoming messages from c->read_cores / read_bonds (the
+// live slab, or the snapshot taken by mpbp_sweep when a Jacobi sweep has to be split), writes the live slab.
+static int sweep_nodes(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_trunc trunc, double damp, const SweepEnv& env, mpbp_stats* stats) {
+  EventPair evs;
+  hipEventRecord(evs.a, c->stream);
+  HIPCHK(c, hipMemsetAsync(c->d_stats, 0, sizeof(EngStats), c->stream));
+  Pass ps{c, env, trunc, damp};
+  SweepPlan sp;
+  std::vector<DevTrain> tr;         // the trains of sp.specs (same indexing)
+  RCCHK(plan_sweep(c, nodes, n_nodes, damp, sp));
+  RCCHK(allocate_trains(c, sp, env, tr));
+  RCCHK(run_prep(c, sp, tr));
+  if (sp.any_generic) RCCHK(run_kron(c, sp, tr));
+  RCCHK(run_cavity(ps, sp, tr));
+  RCCHK(finalise(ps, sp, tr));
+  return read_back(ps, nodes, n_nodes, evs, stats);
+}
 static void merge_stats(mpbp_stats& a, const mpbp_stats& b) {
   a.maxerr = std::max(a.maxerr, b.maxerr); a.n_compress += b.n_compress;
   a.nan_flag |= b.nan_flag; a.capacity_flag |= b.capacity_flag; a.jacobi_not_converged |= b.jacobi_not_converged;
@@ -1166,20 +1159,51 @@ static void merge_stats(mpbp_stats& a, const mpbp_stats& b) {
   a.jacobi_sweeps += b.jacobi_sweeps; a.jacobi_calls += b.jacobi_calls;
 }
 
-static int sweep_split(mpbp_ctx* c, const int32_t* nodes, int32_t n, mpbp_trunc trunc, double damp, mpbp_stats* acc) {
+static int sweep_split(mpbp_ctx* c, const int32_t* nodes, int32_t n, mpbp_trunc trunc, double damp, const SweepEnv& env, mpbp_stats* acc) {
   mpbp_stats st{};
-  int rc = sweep_nodes(c, nodes, n, trunc, damp, &st, true);
+  int rc = sweep_nodes(c, nodes, n, trunc, damp, env, &st);
   if (rc == MPBP_ESPLIT_INTERNAL) {
     const int h = n / 2;
-    rc = sweep_split(c, nodes, h, trunc, damp, acc);
+    rc = sweep_split(c, nodes, h, trunc, damp, env, acc);
     if (rc != MPBP_OK && rc != MPBP_ECAPACITY) return rc;
-    const int rc2 = sweep_split(c, nodes + h, n - h, trunc, damp, acc);
+    const int rc2 = sweep_split(c, nodes + h, n - h, trunc, damp, env, acc);
     return rc2 != MPBP_OK ? rc2 : rc;
   }
   if (rc == MPBP_OK || rc == MPBP_ECAPACITY) merge_stats(*acc, st);
   return rc;
 }
-
+// The listed nodes are updated from the messages at entry (Jacobi semantics of one call): the halves read a
+// snapshot, so that the split is invisible in the results.  Only the in-edges of the listed nodes are read by a pass
+// (prep), so only their slots are copied - the snapshot is allocated exactly when memory is short, and a copy of the
+// whole slab (24 GB at configs[2]) could be what does not fit.
+static int sweep_from_snapshot(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_trunc trunc, double damp, const SweepEnv& env, mpbp_stats* stats) {
+  c->snap_index.assign(c->slot_of_edge.size(), -1);
+  std::vector<int> ins;
+  for (int k = 0; k < n_nodes; k++)
+    for (int p = c->nbr_ptr[nodes[k]]; p < c->nbr_ptr[nodes[k] + 1]; p++) {
+      const int e = c->in_edge[p];
+      if (c->snap_index[e] < 0) { c->snap_index[e] = (int32_t)ins.size(); ins.push_back(e); }
+    }
+  const size_t nin = std::max<size_t>(ins.size(), 1);
+  const size_t cb = sizeof(double) * (size_t)c->slot_doubles * nin, bb = sizeof(int32_t) * (size_t)(c->L + 1) * nin;
+  void* snap = nullptr;
+  hipError_t e = hipMalloc(&snap, cb + bb + 256);
+  if (e != hipSuccess) return c->fail(MPBP_ENOMEM, "hipMalloc(%zu MiB message snapshot for a split sweep) failed", (cb + bb) >> 20);
+  double* sc = (double*)snap; int32_t* sb = (int32_t*)((char*)snap + ((cb + 255) & ~size_t(255)));
+  for (size_t k = 0; k < ins.size(); k++) {
+    hipMemcpyAsync(sc + (int64_t)k * c->slot_doubles, c->slot_cores(ins[k]), sizeof(double) * c->slot_doubles, hipMemcpyDeviceToDevice, c->stream);
+    hipMemcpyAsync(sb + (int64_t)k * (c->L + 1), c->slot_bonds(ins[k]), sizeof(int32_t) * (c->L + 1), hipMemcpyDeviceToDevice, c->stream);
+  }
+  c->snap_cores = sc; c->snap_bonds = sb;
+  mpbp_stats st{};
+  const int rc = sweep_split(c, nodes, n_nodes, trunc, damp, env, &st);
+  hipStreamSynchronize(c->stream);
+  c->snap_cores = nullptr; c->snap_bonds = nullptr;
+  hipFree(snap);
+  c->last = st;
+  if (stats) *stats = st;
+  return rc;
+}
 extern "C" int mpbp_sweep(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mpbp_trunc trunc, double damp, mpbp_stats* stats) {
   if (!c) return MPBP_EINVAL;
   if (n_nodes < 0 || (n_nodes > 0 && !nodes)) return c->fail(MPBP_EINVAL, "bad node list");
@@ -1195,38 +1219,10 @@ extern "C" int mpbp_sweep(mpbp_ctx* c, const int32_t* nodes, int32_t n_nodes, mp
     seen[nodes[k]] = 1;
   }
   c->snap_cores = nullptr; c->snap_bonds = nullptr;
+  const SweepEnv env = read_sweep_env();
   mpbp_stats st{};
-  int rc = sweep_nodes(c, nodes, n_nodes, trunc, damp, &st, true);
-  if (rc == MPBP_ESPLIT_INTERNAL) {
-    // The listed nodes are updated from the messages at entry (Jacobi semantics of one call): the halves read a
-    // snapshot, so that the split is invisible in the results.  Only the in-edges of the listed nodes are read by a pass
-    // (prep), so only their slots are copied - the snapshot is allocated exactly when memory is short, and a copy of the
-    // whole slab (24 GB at configs[2]) could be what does not fit.
-    c->snap_index.assign(c->slot_of_edge.size(), -1);
-    std::vector<int> ins;
-    for (int k = 0; k < n_nodes; k++)
-      for (int p = c->nbr_ptr[nodes[k]]; p < c->nbr_ptr[nodes[k] + 1]; p++) {
-        const int e = c->in_edge[p];
-        if (c->snap_index[e] < 0) { c->snap_index[e] = (int32_t)ins.size(); ins.push_back(e); }
-      }
-    const size_t nin = std::max<size_t>(ins.size(), 1);
-    const size_t cb = sizeof(double) * (size_t)c->slot_doubles * nin, bb = sizeof(int32_t) * (size_t)(c->L + 1) * nin;
-    void* snap = nullptr;
-    hipError_t e = hipMalloc(&snap, cb + bb + 256);
-    if (e != hipSuccess) return c->fail(MPBP_ENOMEM, "hipMalloc(%zu MiB message snapshot for a split sweep) failed", (cb + bb) >> 20);
-    double* sc = (double*)snap; int32_t* sb = (int32_t*)((char*)snap + ((cb + 255) & ~size_t(255)));
-    for (size_t k = 0; k < ins.size(); k++) {
-      hipMemcpyAsync(sc + (int64_t)k * c->slot_doubles, c->slot_cores(ins[k]), sizeof(double) * c->slot_doubles, hipMemcpyDeviceToDevice, c->stream);
-      hipMemcpyAsync(sb + (int64_t)k * (c->L + 1), c->slot_bonds(ins[k]), sizeof(int32_t) * (c->L + 1), hipMemcpyDeviceToDevice, c->stream);
-    }
-    c->snap_cores = sc; c->snap_bonds = sb;
-    st = mpbp_stats{};
-    rc = sweep_split(c, nodes, n_nodes, trunc, damp, &st);
-    hipStreamSynchronize(c->stream);
-    c->snap_cores = nullptr; c->snap_bonds = nullptr;
-    hipFree(snap);
-    c->last = st;
-  }
+  const int rc = sweep_nodes(c, nodes, n_nodes, trunc, damp, env, &st);
+  if (rc == MPBP_ESPLIT_INTERNAL) return sweep_from_snapshot(c, nodes, n_nodes, trunc, damp, env, stats);
   if (stats) *stats = c->last;
   return rc;
 }

@@ -98,15 +98,29 @@ static LookAhead* lookahead_streams() {
   return l.ok ? &l : nullptr;
 }
 // dynamic-LDS limits of the batched QR's kernels: an attribute belongs to the (function, device) pair, so it is set once
-// per device (it used to be set 6-7 times per qr_batch call, ~400 intercepted API calls per gauge sweep)
-static void set_func_attrs_once() {
+// per device (it used to be set 6-7 times per qr_batch call, ~400 intercepted API calls per gauge sweep).  The flag is
+// published only after every call has succeeded, under the mutex, so that no thread launches before they have run.
+static hipError_t set_func_attrs() {
+  const std::pair<const void*, int> lim[] = {
+      {(const void*)v2::k_fpanel, (int)v2::fpanel_lds_bytes(3)},
+      {(const void*)cq::k_cq_upd<256>, cq::UPD_LDS_DOUBLES * 8},
+      {(const void*)cq::k_cq_updfac, cq::UPD_LDS_DOUBLES * 8},
+      {(const void*)cq::k_cq_fac2, cq::FAC_LDS_DOUBLES * 8},
+      {(const void*)v2::k_jac_block, 152 * 1024}};
+  for (const auto& l : lim) {
+    const hipError_t e = hipFuncSetAttribute(l.first, hipFuncAttributeMaxDynamicSharedMemorySize, l.second);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+static hipError_t set_func_attrs_once() {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) dev = -1;
-  if (dev >= 0) { std::lock_guard<std::mutex> lk(g_dev[dev].mu); if (g_dev[dev].attrs) return; g_dev[dev].attrs = true; }
-  hipFuncSetAttribute((const void*)v2::k_fpanel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v2::fpanel_lds_bytes(3));
-  hipFuncSetAttribute((const void*)cq::k_cq_upd<256>, hipFuncAttributeMaxDynamicSharedMemorySize, cq::UPD_LDS_DOUBLES * 8);
-  hipFuncSetAttribute((const void*)cq::k_cq_updfac, hipFuncAttributeMaxDynamicSharedMemorySize, cq::UPD_LDS_DOUBLES * 8);
-  hipFuncSetAttribute((const void*)v2::k_jac_block, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return set_func_attrs();
+  std::lock_guard<std::mutex> lk(g_dev[dev].mu);
+  if (g_dev[dev].attrs) return hipSuccess;
+  const hipError_t e = set_func_attrs();
+  g_dev[dev].attrs = e == hipSuccess;
+  return e;
 }
 
 // Launch sequence of one R-only QR over a batch whose dimensions `dims` are known on the host.
@@ -128,7 +142,7 @@ int qr_batch(hipStream_t st, const v2::QrProb* d_probs, const std::vector<QrDims
   }
   const int nchunk = (rows32_max + v2::CH - 1) / v2::CH;
   if (nchunk > lay.nchunk) return -1;
-  set_func_attrs_once();
+  if (set_func_attrs_once() != hipSuccess) return -2;
   static const bool no_coop = getenv("MPBP_DEBUG_NO_COOP_PANEL") != nullptr;
 
   // ---- the panel chain of block jb (4 panels: in-block update, column steps, Gram, T) on stream s with scratch layout L
@@ -495,7 +509,7 @@ static int jacobi_selftest(int32_t device, int32_t m, int32_t n, const double* A
   D.JA = dJA; D.Rr = m; D.r1 = n; D.scal = dscal; D.act = dact;
   ST2CHK(hipMemcpy(dd, &D, sizeof D, hipMemcpyHostToDevice));
   if (block) {
-    set_func_attrs_once();
+    ST2CHK(set_func_attrs_once());
     const int nb = jac_block_nb(m, n);
     if (nb < 2) { g_create_error = "factor too tall for an LDS-resident block pair"; return MPBP_EUNSUPPORTED; }
     const int nblk = (n + nb - 1) / nb, ne = (nblk + 1) & ~1;

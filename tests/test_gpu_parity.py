@@ -961,6 +961,27 @@ def test_single_wave_engine_variant_forced(monkeypatch):
         assert np.array_equal(bp.bonds(), np.array([m.bonds for m in obp.mu]))
 
 
+@pytest.mark.parametrize("force_small", [False, True])
+def test_level_by_level_cavity_fallback_forced(force_small, monkeypatch):
+    """The cavity products normally launch by readiness; when a 512-thread product reads a single-wave result above
+    level 1 the sweep falls back to launching them level by level.  MPBP_DEBUG_NO_PACK=1 forces that fallback on a loopy
+    SIS model (with MPBP_DEBUG_FORCE_SMALL=1 and max_bond 4 both engine variants run at every level): oracle parity."""
+    monkeypatch.setenv("MPBP_DEBUG_NO_PACK", "1")
+    if force_small:
+        monkeypatch.setenv("MPBP_DEBUG_FORCE_SMALL", "1")
+    N, T, Mb = 8, 6, 4 if force_small else 6
+    lam, rho, gam = 0.2, 0.1, 0.15
+    A, phi = _loopy(N, T, lam, rho, gam)
+    bp = M.mpbp(M.IndexedBiDiGraph(A), [[M.SISFactor(lam, rho)] * (T + 1)] * N, 2, T, phi=phi, max_bond=Mb)
+    obp = O.mpbp(O.IndexedBiDiGraph(A), [[OF.SISFactor(lam, rho)] * (T + 1)] * N, [2] * N, T, phi=phi)
+    for s in range(3):
+        M.iterate(bp, maxiter=1, svd_trunc=M.TruncBond(Mb), tol=0.0)
+        O.iterate(obp, maxiter=1, svd_trunc=OT.TruncBond(Mb), tol=0.0, shuffle_nodes=False, jacobi=True)
+        assert _rel(_flat(M.beliefs(bp)), _flat(O.beliefs(obp))) < RTOL, f"sweep {s}"
+        assert np.abs(_fnodes(bp) - obp.f).max() < RTOL * max(1.0, np.abs(obp.f).max()), f"sweep {s}"
+    assert np.array_equal(bp.bonds(), np.array([m.bonds for m in obp.mu]))
+
+
 def test_autocorrelations_match_enumeration():
     """reference test/sis_small_tree.jl:36-49: two-time observables from the belief trains (`bp.b[i]`)."""
     from oracle.exact import exact_autocorrelations
