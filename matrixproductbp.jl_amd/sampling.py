@@ -192,19 +192,20 @@ def autocorrelations(f, sms: SoftMarginSampler, sites=None, maxdist=None):
 
 
 def autocovariances(f, sms: SoftMarginSampler, sites=None, maxdist=None):
-    """`autocovariances(f, sms)` (src/sampling.jl:185-191): `r - mu mu'` with first-order error propagation."""
+    """`autocovariances(f, sms)` (src/sampling.jl:179-185): `covariance(r, mu) = r - mu mu'` (src/mpbp.jl:288) over the
+    whole (T+1) x (T+1) matrix, as `mpbp.autocovariances` does - outside the window t < u <= t + maxdist, where r is 0, the
+    entry is -mu_t mu_u.  Errors to first order: sqrt(re^2 + (mu_u s_t)^2 + (mu_t s_u)^2) off the diagonal and, the two
+    factors being one variable there, 2 |mu_t| s_t on it."""
     sites = list(sms.sites) if sites is None else [int(i) for i in sites]
     r, re = autocorrelations(f, sms, sites, maxdist)
     mu, me = means(f, sms, sites)
-    L = sms.bp.T + 1
-    md = sms.maxdist if maxdist is None else int(maxdist)
-    t, u = np.indices((L, L))
-    mask = (t < u) & (u <= t + md)
     cv, ce = [], []
     for a in range(len(sites)):
         m, s = mu[a], me[a]
-        cv.append(np.where(mask, r[a] - np.outer(m, m), 0.0))
-        ce.append(np.where(mask, np.sqrt(re[a] ** 2 + np.outer(s, m) ** 2 + np.outer(m, s) ** 2), 0.0))
+        cv.append(r[a] - np.outer(m, m))
+        e = np.sqrt(re[a] ** 2 + np.outer(s, m) ** 2 + np.outer(m, s) ** 2)
+        np.fill_diagonal(e, 2 * np.abs(m) * s)
+        ce.append(e)
     return cv, ce
 
 

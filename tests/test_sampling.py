@@ -162,8 +162,9 @@ def _draw_raw(sms, n):
 STAR = np.array([[0, 1, 1, 1], [1, 0, 0, 0], [1, 0, 0, 0], [1, 0, 0, 0]])
 
 
-def _star_sis(T=2, observe=False, psi=False, seed=111):
-    """reference test/sampling.jl:1-20: SIS(g, λ=0.5, ρ=0.2, T; γ=0.5, α=0.1) on the star of 4"""
+def _star_sis(T=2, observe=False, psi=False, seed=111, host=False):
+    """reference test/sampling.jl:1-20: SIS(g, λ=0.5, ρ=0.2, T; γ=0.5, α=0.1) on the star of 4 (host: the same model as a
+    _HostModel, built and observed without a device)"""
     lam, rho, gam, alpha = 0.5, 0.2, 0.5, 0.1
     phi = [[np.array([1 - gam, gam]) if t == 0 else np.ones(2) for t in range(T + 1)] for _ in range(4)]
     g = M.IndexedBiDiGraph(STAR)
@@ -177,6 +178,11 @@ def _star_sis(T=2, observe=False, psi=False, seed=111):
             if key not in base:
                 base[key] = [rng.random((2, 2)) + 0.2 for _ in range(T + 1)]
             ps.append([m if i < j else m.T.copy() for m in base[key]])
+    if host:
+        hm = _HostModel(g, [[M.SISFactor(lam, rho, alpha)] * (T + 1)] * 4, 2, T, phi=phi, psi=ps)
+        if observe:
+            _host_observe(hm, 4, last_time=True, softinf=1e2, rng=np.random.default_rng(seed))
+        return hm
     bp = M.mpbp(g, [[M.SISFactor(lam, rho, alpha)] * (T + 1)] * 4, 2, T, phi=phi, psi=ps, max_bond=16)
     if observe:
         M.draw_node_observations(bp, 4, last_time=True, softinf=1e2, rng=np.random.default_rng(seed))
@@ -216,14 +222,27 @@ def _sirs_tree():
     return M.mpbp(M.IndexedBiDiGraph(A), [[M.SIRSFactor(0.4, 0.4, 0.3, 0.05)] * (T + 1)] * 3, 3, T, phi=phi, max_bond=27)
 
 
-def _hetero_tree():
+def _hetero_tree(extended=False):
+    """extended: with rectangular non-symmetric psi (psi_ji = psi_ij') and two soft observations"""
     T = 2
     A = np.array([[0, 1, 1, 0], [1, 0, 0, 1], [1, 0, 0, 0], [0, 1, 0, 0]])
     qs = [2, 3, 2, 3]
     rng = np.random.default_rng(0)
     phi = [[rng.random(q) + 0.1 for _ in range(T + 1)] for q in qs]
     w = [[M.SISFactor(0.3, 0.2)] * (T + 1) if q == 2 else [M.SIRSFactor(0.3, 0.2, 0.1)] * (T + 1) for q in qs]
-    return M.mpbp(M.IndexedBiDiGraph(A), w, qs, T, phi=phi, max_bond=16)
+    g = M.IndexedBiDiGraph(A)
+    ps = None
+    if extended:
+        base, ps = {}, []
+        for (i, j, _) in g.edges():
+            key = (min(i, j), max(i, j))
+            if key not in base:
+                base[key] = [rng.random((qs[key[0]], qs[key[1]])) + 0.2 for _ in range(T + 1)]
+            ps.append([m if i < j else m.T.copy() for m in base[key]])
+        assert {m[0].shape for m in ps} == {(2, 3), (3, 2), (2, 2), (3, 3)}
+        for (i, t, x) in ((1, 2, 2), (2, 1, 0)):     # node i seen in state x at time t, softinf = 30
+            phi[i][t] = phi[i][t] * np.where(np.arange(qs[i]) == x, 30.0 / 31.0, 1.0 / 31.0)
+    return M.mpbp(g, w, qs, T, phi=phi, psi=ps, max_bond=16)
 
 
 def _generic_star():
@@ -525,3 +544,498 @@ def test_sampler_error_paths_do_not_abort():
     with pytest.raises(M.MPBPError) as ei:
         M.marginals(z)
     assert ei.value.code == -1 and "zero" in str(ei.value)
+
+
+# ================================================================================================ weighted accumulators
+# The second half of the sampler - k_weights, k_acc_node, k_acc_pair, k_acc_corr and the four read-outs - against a
+# plain high-precision accumulation of the very (X, log w) the device returned.
+U = 2.0 ** -53
+LDBL = np.longdouble
+
+
+class _HostModel:
+    """What HostSampler reads of an MPBP - graph, factors, states per node, phi and psi in the mirror's padded layout -
+    without a device context, so that seeds are chosen and checked where there is no GPU."""
+
+    def __init__(self, g, w, q, T, phi=None, psi=None):
+        N = g.nv()
+        qn = np.atleast_1d(np.asarray(q, dtype=np.int64))
+        self.qnode = (np.full(N, int(qn[0])) if qn.size == 1 else qn).astype(np.int32)
+        self.g, self.w, self.q, self.T = g, w, int(self.qnode.max()), int(T)
+        self.phi = np.zeros((self.q, T + 1, N))
+        self.psi = np.zeros((self.q, self.q, T + 1, g.ne()))
+        for i in range(N):
+            for t in range(T + 1):
+                self.phi[:self.qnode[i], t, i] = 1.0 if phi is None else phi[i][t]
+        for (i, j, e) in g.edges():
+            for t in range(T + 1):
+                self.psi[:self.qnode[i], :self.qnode[j], t, e] = 1.0 if psi is None else psi[e][t]
+
+
+def _host_observe(hm, nobs, softinf=np.inf, last_time=False, rng=None):
+    """draw_node_observations on a _HostModel: the same calls of rng, the prior trajectory from HostSampler"""
+    N, T = hm.g.nv(), hm.T
+    X, _, near = HostSampler(hm).trajectories(int(rng.integers(0, 2 ** 63 - 1)), [0])
+    assert not near.any()
+    X = X[0].T + 1
+    pairs = [(i, t) for t in (range(T, T + 1) if last_time else range(T + 1)) for i in range(N)]
+    observed = sorted(pairs[k] for k in rng.choice(len(pairs), size=int(nobs), replace=False))
+    with np.errstate(divide="ignore"):
+        lsi = np.log(softinf)
+    softone, softzero = 1.0 / (1.0 + np.exp(-lsi)), 1.0 / (1.0 + np.exp(lsi))
+    for (i, t) in observed:
+        for x in range(hm.qnode[i]):
+            hm.phi[x, t, i] *= softone if x == X[i, t] - 1 else softzero
+    return X, observed
+
+
+def _set_inputs(bp, phi=None, psi=None):
+    """new phi / psi of a live context: the host mirror, and the device through mpbp_set_phi / mpbp_set_psi"""
+    if phi is not None:
+        bp.phi[...] = phi
+        M._lib.check(bp._L.mpbp_set_phi(bp._h, bp.phi.ravel(order="F").ctypes.data_as(C.POINTER(C.c_double))), bp._h)
+    if psi is not None:
+        bp.psi[...] = psi
+        M._lib.check(bp._L.mpbp_set_psi(bp._h, bp.psi.ravel(order="F").ctypes.data_as(C.POINTER(C.c_double))), bp._h)
+
+
+class Acc:
+    """node[i, t, x], pair[e, t, x_src, x_dst], corr[k, t, u, x_t, x_u] (exactly 0 outside t < u <= t + maxdist; None
+    without sites), log sum w, log sum w^2, log ESS.  Probabilities are None where every weight is zero."""
+
+    def __init__(self, node, pair, corr, log_sw, log_sw2, log_ess=None):
+        self.node, self.pair, self.corr, self.log_sw, self.log_sw2 = node, pair, corr, log_sw, log_sw2
+        self.log_ess = 2 * log_sw - log_sw2 if log_ess is None else log_ess
+
+
+def _weighted_counts(w, codes, nbins):
+    """out[k, ...] = sum_s w[s] [codes[s, ...] == k] in long double, over slabs of samples to bound the temporaries"""
+    out = np.zeros((nbins,) + codes.shape[1:], dtype=LDBL)
+    step = max(1, (1 << 22) // max(1, int(np.prod(codes.shape[1:]))))
+    for a in range(0, len(w), step):
+        c, wc = codes[a:a + step], w[a:a + step].reshape((-1,) + (1,) * (codes.ndim - 1))
+        for k in range(nbins):
+            out[k] += np.add.reduce(np.broadcast_to(wc, c.shape), axis=0, where=(c == k))
+    return out
+
+
+def reference_accumulators(X, logw, ends, q, sites=(), maxdist=None):
+    """The importance-weighted marginals of trajectories X [n, T+1, N] (0-based states) with log-weights logw [n]:
+    every weight is exp(log w - max log w) in long double (log w = -inf weighs exactly 0), every sum is a long-double
+    sum over all n samples at once - no batches, no running maximum, no rescaling.  ends[e] = (src, dst) node of edge e."""
+    X = np.asarray(X)
+    n, L, N = X.shape
+    lw = np.asarray(logw, dtype=LDBL)
+    assert lw.shape == (n,) and not np.isnan(lw).any() and not np.isposinf(lw).any()
+    top = lw.max()
+    ninf = float("-inf")
+    if np.isneginf(top):
+        return Acc(None, None, None, ninf, ninf, log_ess=ninf)
+    with np.errstate(under="ignore"):
+        w = np.where(np.isneginf(lw), LDBL(0), np.exp(lw - top))
+        w2 = np.where(np.isneginf(lw), LDBL(0), np.exp(2 * (lw - top)))
+    sw, sw2 = w.sum(dtype=LDBL), w2.sum(dtype=LDBL)
+    log_sw, log_sw2 = top + np.log(sw), 2 * top + np.log(sw2)
+    node = np.moveaxis(_weighted_counts(w, X, q), 0, -1) / sw                          # [L, N, q]
+    src, dst = np.array([ends[e][0] for e in range(len(ends))]), np.array([ends[e][1] for e in range(len(ends))])
+    pc = _weighted_counts(w, X[:, :, src].astype(np.int16) + q * X[:, :, dst], q * q) / sw   # [x_src + q x_dst, L, E]
+    pair = pc.reshape(q, q, L, len(ends)).transpose(3, 2, 1, 0)                        # [e, t, x_src, x_dst]
+    corr = None
+    if len(sites):
+        D = L - 1 if maxdist is None else int(maxdist)
+        corr = np.zeros((len(sites), L, L, q, q), dtype=LDBL)
+        Xs = X[:, :, list(sites)].astype(np.int16)
+        for t in range(L):
+            for u in range(t + 1, min(L, t + D + 1)):
+                cc = _weighted_counts(w, Xs[:, t] + q * Xs[:, u], q * q) / sw         # [x_t + q x_u, k]
+                corr[:, t, u] = cc.reshape(q, q, len(sites)).transpose(2, 1, 0)
+    f = lambda a: None if a is None else np.asarray(a, dtype=np.float64)
+    return Acc(f(node.transpose(1, 0, 2)), f(pair), f(corr), float(log_sw), float(log_sw2),
+               log_ess=float(2 * log_sw - log_sw2))
+
+
+def naive_accumulators(X, logw, ends, q, sites=(), maxdist=None):
+    """The same quantities the slowest way: one Python loop over the samples, w = exp(log w) with no shift at all, one
+    list of weights per histogram bin, math.fsum of every list."""
+    import math
+    n, L, N = X.shape
+    D = L - 1 if maxdist is None else int(maxdist)
+    ws, node, pair, corr = [], {}, {}, {}
+    for s in range(n):
+        w = math.exp(logw[s])
+        ws.append(w)
+        for t in range(L):
+            for i in range(N):
+                node.setdefault((i, t, int(X[s, t, i])), []).append(w)
+            for e, (i, j) in enumerate(ends):
+                pair.setdefault((e, t, int(X[s, t, i]), int(X[s, t, j])), []).append(w)
+            for k, i in enumerate(sites):
+                for u in range(t + 1, min(L, t + D + 1)):
+                    corr.setdefault((k, t, u, int(X[s, t, i]), int(X[s, u, i])), []).append(w)
+    sw, sw2 = math.fsum(ws), math.fsum(w * w for w in ws)
+    out = Acc(np.zeros((N, L, q)), np.zeros((len(ends), L, q, q)), np.zeros((len(sites), L, L, q, q)) if len(sites) else None,
+              math.log(sw), math.log(sw2))
+    for dst, bins in ((out.node, node), (out.pair, pair), (out.corr, corr)):
+        for key, lst in bins.items():
+            dst[key] = math.fsum(lst) / sw
+    return out
+
+
+def _running_max_steps(logw, calls):
+    """increase of the running maximum of log w from the end of one call to the end of the next"""
+    ends_ = np.cumsum(calls)
+    assert ends_[-1] <= len(logw)
+    return np.diff([np.max(logw[:b]) for b in ends_])
+
+
+def _assert_maximum_moves(logw, calls):
+    steps = _running_max_steps(logw, calls)
+    assert (steps > 0).sum() >= 2 and steps.max() > np.log(2), steps
+
+
+SEED_A = 1                  # chosen on the host: test_case_a_seed_moves_the_running_maximum
+HARD_OBS_RNG, SEED_HARD = 1, 1   # chosen on the host: test_hard_observation_seed_excludes_sample_zero
+
+
+def _hard_observed_star(host=False):
+    """star of 4, T = 3, psi, two hard observations at the last time (draw_node_observations, softinf = inf)"""
+    bp = _star_sis(T=3, psi=True, host=host)
+    rng = np.random.default_rng(HARD_OBS_RNG)
+    if host:
+        _host_observe(bp, 2, last_time=True, rng=rng)
+    else:
+        M.draw_node_observations(bp, 2, last_time=True, rng=rng)
+    return bp
+
+
+def test_reference_accumulators_match_naive_loop():
+    hm = _star_sis(T=3, observe=True, psi=True, host=True)
+    X, lw, _ = HostSampler(hm).trajectories(0xACC, np.arange(200))
+    assert np.ptp(lw) > 1.0
+    lw[[5, 77]] = -np.inf                                    # two excluded trajectories among weighted ones
+    ends = [(i, j) for (i, j, _) in hm.g.edges()]
+    for sites, md in (([2, 0], 2), ([1], None), ((), None)):
+        ref = reference_accumulators(X, lw, ends, 2, sites, md)
+        nv = naive_accumulators(X, lw, ends, 2, sites, md)
+        for name in ("node", "pair", "corr"):
+            a, b = getattr(ref, name), getattr(nv, name)
+            assert (a is None and b is None) or np.abs(a - b).max() <= 1e-15, name
+        assert abs(ref.node.sum(axis=2) - 1).max() <= 1e-15 and abs(ref.pair.sum(axis=(2, 3)) - 1).max() <= 1e-15
+        for name in ("log_sw", "log_sw2", "log_ess"):
+            a, b = getattr(ref, name), getattr(nv, name)
+            assert abs(a - b) <= 1e-15 * max(1.0, abs(b)), name
+    ref = reference_accumulators(X, lw, ends, 2, [2, 0], 2)
+    L = hm.T + 1
+    for t in range(L):
+        for u in range(L):
+            if not t < u <= t + 2:
+                assert np.all(ref.corr[:, t, u] == 0.0)
+            else:                                            # the joint's two margins are the node marginals
+                for k, i in enumerate([2, 0]):
+                    assert np.abs(ref.corr[k, t, u].sum(axis=1) - ref.node[i, t]).max() <= 1e-15
+                    assert np.abs(ref.corr[k, t, u].sum(axis=0) - ref.node[i, u]).max() <= 1e-15
+    # far below the range of exp the shift keeps every ratio of weights (log w on a 2^-20 grid: subtracting 5000 is exact)
+    lwq = np.round(lw * 2.0 ** 20) / 2.0 ** 20
+    ref, deep = (reference_accumulators(X, v, ends, 2, [2, 0], 2) for v in (lwq, lwq - 5000.0))
+    assert np.exp(lwq[np.isfinite(lwq)] - 5000.0).max() == 0.0
+    assert np.abs(deep.node - ref.node).max() <= 1e-15 and np.abs(deep.corr - ref.corr).max() <= 1e-15
+    assert abs(deep.log_sw - (ref.log_sw - 5000.0)) <= 1e-12 and abs(deep.log_ess - ref.log_ess) <= 1e-15
+    none = reference_accumulators(X, np.full(200, -np.inf), ends, 2)
+    assert none.node is None and none.log_sw == -np.inf and none.log_ess == -np.inf
+
+
+def test_case_a_seed_moves_the_running_maximum():
+    """case A of test_device_accumulators_match_reference: over its calls of 1, 10 and 1000 samples the running maximum of
+    log w rises at the end of each of the last two, once by more than log 2 - asserted here from the host restatement."""
+    hm = _star_sis(T=3, observe=True, psi=True, host=True)
+    _, lw, near = HostSampler(hm).trajectories(SEED_A, np.arange(1011))
+    top = [lw[:1].max(), lw[:11].max(), lw.max()]
+    assert not near[[int(np.argmax(lw[:b])) for b in (1, 11, 1011)]].any()
+    _assert_maximum_moves(lw, (1, 10, 1000))
+    assert top[0] < top[1] < top[2]
+
+
+def test_hard_observation_seed_excludes_sample_zero():
+    hm = _hard_observed_star(host=True)
+    assert (hm.phi[:, 3, :] == 0).sum() == 2                # two hard observations, at the last time
+    _, lw, near = HostSampler(hm).trajectories(SEED_HARD, np.arange(200))
+    assert lw[0] == -np.inf and not near[0]
+    assert 0.1 < np.isneginf(lw).mean() < 0.9
+
+
+# ------------------------------------------------------------------------------------------------ GPU: accumulators
+def _new_sampler(bp, seed, sites, maxdist):
+    return M.SoftMarginSampler(bp, seed=seed, autocorr_sites=sites, maxdist=maxdist)
+
+
+def _read_device(sms):
+    """the four C read-outs of a sampler as an Acc, and the sample count"""
+    bp, Lb = sms.bp, sms._L
+    N, E, L, q, nc = bp.g.nv(), bp.g.ne(), bp.T + 1, bp.q, len(sms.sites)
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    node, pair, corr = np.full(q * L * N, np.nan), np.full(q * q * L * E, np.nan), np.full(nc * L * L * q * q, np.nan)
+    sms._check(Lb.mpbp_sampler_marginals(sms._h, dp(node)))
+    sms._check(Lb.mpbp_sampler_pair_marginals(sms._h, dp(pair)))
+    if nc:
+        sms._check(Lb.mpbp_sampler_twovar_marginals(sms._h, dp(corr)))
+    n, a, b = C.c_int64(), C.c_double(), C.c_double()
+    sms._check(Lb.mpbp_sampler_counts(sms._h, C.byref(n), C.byref(a), C.byref(b)))
+    return Acc(node.reshape(N, L, q), pair.reshape(E, L, q, q).transpose(0, 1, 3, 2),
+               corr.reshape(nc, L, L, q, q).transpose(0, 1, 2, 4, 3) if nc else None, a.value, b.value), int(n.value)
+
+
+def _tolerances(n, ref):
+    """Derived, not measured.  A probability is a ratio of two recursive fp64 sums of n non-negative terms, each within
+    n u relative (u = 2^-53), hence 4 n u with the two sums' own terms rounded; the floor of 1024 covers the
+    |log w - M| u rounding of the exponent's argument and the rescales at batch boundaries.  log sum w adds the rounding
+    of M + log(sw), 2^-52 |value|; log ESS = 2 log sum w - log sum w^2 takes three of those."""
+    tp = 4 * max(n, 1024) * U
+    tl = lambda v: tp + 2.0 ** -52 * abs(v)
+    return tp, tl(ref.log_sw), tl(ref.log_sw2), 3 * tl(ref.log_sw)
+
+
+def _assert_matches(dev, n_dev, ref, n, maxdist, label):
+    """every read-out of the device within its derived bound of the reference; the figures are printed first"""
+    assert n_dev == n
+    tp, tsw, tsw2, tess = _tolerances(n, ref)
+    fig = {"node": np.abs(dev.node - ref.node).max(), "pair": np.abs(dev.pair - ref.pair).max(),
+           "corr": np.abs(dev.corr - ref.corr).max() if ref.corr is not None else 0.0,
+           "log_sw": abs(dev.log_sw - ref.log_sw), "log_sw2": abs(dev.log_sw2 - ref.log_sw2),
+           "log_ess": abs(dev.log_ess - ref.log_ess)}
+    bound = {"node": tp, "pair": tp, "corr": tp, "log_sw": tsw, "log_sw2": tsw2, "log_ess": tess}
+    print(f"[{label}] n = {n}: " + ", ".join(f"{k} {fig[k]:.3e} (bound {bound[k]:.3e})" for k in fig))
+    for arr in (dev.node, dev.pair, dev.corr):
+        assert arr is None or np.all(np.isfinite(arr))
+    assert np.isfinite([dev.log_sw, dev.log_sw2]).all()
+    for k in fig:
+        assert fig[k] <= bound[k], (label, k, fig[k], bound[k])
+    if ref.corr is not None:
+        L = ref.corr.shape[1]
+        t, u = np.indices((L, L))
+        outside = ~((t < u) & (u <= t + maxdist))
+        assert np.all(dev.corr[:, outside] == 0.0) and np.all(ref.corr[:, outside] == 0.0)
+    return fig
+
+
+def _karate_observed():
+    """_karate_glauber with phi^{t>=1} different at every node, time and state"""
+    bp = _karate_glauber()
+    phi = bp.phi.copy()
+    phi[:, 1:, :] = np.random.default_rng(5).random(phi[:, 1:, :].shape) + 0.2
+    _set_inputs(bp, phi=phi)
+    return bp
+
+
+#        model, autocorr sites, maxdist, samples per call on ONE sampler, seed
+ACC_CASES = {"A": (lambda: _star_sis(T=3, observe=True, psi=True), [2, 0], 2, (1, 10, 1000, 2 * 65536 + 777), None),
+             "B": (lambda: _hetero_tree(extended=True), [3, 1], 1, (7, 65536 + 4321), 0xB0B),
+             "C": (_sirs_tree, [0, 1, 2], None, (3000,), 0xC0C),
+             "D": (_karate_observed, list(range(34)), 3, (500, 65536 + 123), 0xD0D)}
+_acc_runs = {}
+
+
+def _acc_run(case):
+    """one sampler per case, drawn once; its (X, log w), the reference over them and the device read-outs are shared by
+    the tests below and left unchanged"""
+    if case not in _acc_runs:
+        make, sites, md, calls, seed = ACC_CASES[case]
+        bp = make()
+        sms = _new_sampler(bp, SEED_A if seed is None else seed, sites, md)
+        Xs, lws = zip(*(_draw_raw(sms, k) for k in calls))
+        X, lw = np.concatenate(Xs), np.concatenate(lws)
+        D = bp.T if md is None else md
+        ends = [bp._ends[e] for e in range(bp.g.ne())]
+        ref = reference_accumulators(X, lw, ends, bp.q, sites, D)
+        for a in (X, lw, ref.node, ref.pair, ref.corr):
+            a.setflags(write=False)
+        dev, n_dev = _read_device(sms)
+        _acc_runs[case] = dict(bp=bp, sms=sms, X=X, lw=lw, ref=ref, dev=dev, n_dev=n_dev, calls=calls, D=D, sites=sites)
+    return _acc_runs[case]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(ACC_CASES))
+def test_device_accumulators_match_reference(case):
+    r = _acc_run(case)
+    bp, lw, calls = r["bp"], r["lw"], r["calls"]
+    N, E, L, nc = bp.g.nv(), bp.g.ne(), bp.T + 1, len(r["sites"])
+    # preconditions: the path this case is here for is live
+    assert len(lw) == sum(calls) and np.all(np.isfinite(lw)) and np.ptp(lw) > 0
+    if case == "A":
+        hm = _star_sis(T=3, observe=True, psi=True, host=True)
+        assert np.array_equal(bp.phi, hm.phi) and np.array_equal(bp.psi, hm.psi)
+        _assert_maximum_moves(lw, calls)
+        assert r["sites"] != sorted(r["sites"]) and r["D"] < bp.T
+    if case in "AB":
+        assert calls[-1] % 32 != 0 and r["D"] < bp.T
+    if case == "A":
+        assert calls[-1] > 2 * 65536                         # at least two batch boundaries inside one call
+    if case == "B":
+        assert sorted(set(int(v) for v in bp.qnode)) == [2, 3] and bp.q == 3
+        assert not np.array_equal(bp.psi[:, :, 0, 0], bp.psi[:, :, 0, 0].T)
+    if case == "C":
+        assert bp.q == 3 and r["D"] == bp.T
+    if case == "D":
+        assert E == 156 and E * L > 256 and nc * L * r["D"] > 256   # several workgroups of k_acc_pair, k_acc_corr
+    _assert_matches(r["dev"], r["n_dev"], r["ref"], len(lw), r["D"], case)
+
+
+@pytest.mark.gpu
+def test_underflowing_weights():
+    """log w < -745 for every sample: exp(log w) is 0 in fp64, the sum the reference implementation divides by."""
+    bp = _star_sis(T=3, psi=True)
+    phi = bp.phi.copy()
+    phi[:, 1:, :] = np.array([1e-100, 3e-101])[:, None, None]
+    _set_inputs(bp, phi=phi)
+    sms = _new_sampler(bp, 41, [0, 3], 3)
+    X, lw = _draw_raw(sms, 5000)
+    assert lw.max() < -745 and np.all(np.isfinite(lw)) and np.ptp(lw) > 1
+    with np.errstate(under="ignore"):
+        assert np.exp(lw).sum() == 0.0
+    ref = reference_accumulators(X, lw, [bp._ends[e] for e in range(bp.g.ne())], 2, [0, 3], 3)
+    dev, n = _read_device(sms)
+    _assert_matches(dev, n, ref, 5000, 3, "underflow")
+    assert M.effective_sample_size(sms) > 1
+
+
+@pytest.mark.gpu
+def test_hard_observations_zero_weights_then_recovery():
+    bp = _hard_observed_star()
+    hm = _hard_observed_star(host=True)
+    assert np.array_equal(bp.phi, hm.phi) and np.array_equal(bp.psi, hm.psi)
+    sms = M.SoftMarginSampler(bp, seed=SEED_HARD, keep_samples=True, autocorr_sites=[1, 0], maxdist=2)
+    M.sample(sms, 1)
+    assert sms.nsamples == 1 and sms.logw[0] == -np.inf
+    n, a, b = C.c_int64(), C.c_double(), C.c_double()
+    sms._check(sms._L.mpbp_sampler_counts(sms._h, C.byref(n), C.byref(a), C.byref(b)))
+    assert n.value == 1 and a.value == -np.inf and b.value == -np.inf
+    assert M.effective_sample_size(sms) == 0.0
+    for read in (M.marginals, M.pair_marginals, M.sampling.twovar_marginals):
+        with pytest.raises(M.MPBPError) as ei:
+            read(sms)
+        assert ei.value.code == -1
+    M.sample(sms, 20000)
+    assert sms.nsamples == 20001 and len(sms.X) == 20001
+    zero = np.isneginf(sms.logw)
+    assert 0.1 <= zero.mean() <= 0.9 and not np.isnan(sms.logw).any()
+    X = np.array(sms.X).transpose(0, 2, 1) - 1
+    ref = reference_accumulators(X, sms.logw, [bp._ends[e] for e in range(bp.g.ne())], 2, [1, 0], 2)
+    dev, n_dev = _read_device(sms)
+    _assert_matches(dev, n_dev, ref, 20001, 2, "hard observations")
+    assert abs(np.log(M.effective_sample_size(sms)) - ref.log_ess) <= _tolerances(20001, ref)[3] + 4 * U * abs(ref.log_ess)
+
+
+@pytest.mark.gpu
+def test_inputs_changed_under_a_live_sampler():
+    bp = _star_sis(T=3, observe=True, psi=True)
+    seed = 0x5EED
+    sms = _new_sampler(bp, seed, [0, 1], 2)
+    X0, lw0 = _draw_raw(sms, 300)
+    rng = np.random.default_rng(9)
+    phi, psi = bp.phi.copy(), bp.psi.copy()
+    phi[:, 1:, :] = rng.random(phi[:, 1:, :].shape) + 0.1
+    for e in range(bp.g.ne()):
+        r = int(bp.g.rev[e])
+        if e < r:
+            psi[:, :, :, e] = rng.random(psi[:, :, :, e].shape) + 0.3
+            psi[:, :, :, r] = psi[:, :, :, e].transpose(1, 0, 2)
+    assert not np.array_equal(phi, bp.phi) and not np.array_equal(psi, bp.psi)
+    _set_inputs(bp, phi=phi, psi=psi)
+    X1, lw1 = _draw_raw(sms, 300)
+    hX, hlw, near = HostSampler(bp).trajectories(seed, np.arange(300, 600))
+    assert near.sum() < 3
+    ok = ~near
+    assert np.array_equal(X1[ok], hX[ok])
+    np.testing.assert_allclose(lw1[ok], hlw[ok], rtol=0, atol=1e-12)
+    X, lw = np.concatenate([X0, X1]), np.concatenate([lw0, lw1])
+    ref = reference_accumulators(X, lw, [bp._ends[e] for e in range(bp.g.ne())], 2, [0, 1], 2)
+    dev, n = _read_device(sms)
+    _assert_matches(dev, n, ref, 600, 2, "inputs changed")
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the Python layer
+def _close(a, b, scale):
+    """two fp64 evaluations of one formula of at most q^2 = 9 terms of magnitude <= scale: each term and each partial sum
+    rounds once in either order, 2 (9 + 9) u scale < 64 u scale; the same relative slack through the square roots"""
+    np.testing.assert_allclose(a, b, rtol=64 * U, atol=64 * U * scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["A", "B"])
+@pytest.mark.parametrize("fname", ["indicator", "site_dependent"])
+def test_python_layer_matches_restatement(case, fname):
+    """marginals, pair_marginals, means, autocorrelations, autocovariances and effective_sample_size of sampling.py
+    against the reference's definitions (src/sampling.jl:91-185, src/mpbp.jl:288) restated on the raw C read-outs."""
+    r = _acc_run(case)
+    bp, sms, dev, ref, n = r["bp"], r["sms"], r["dev"], r["ref"], len(r["lw"])
+    f = {"indicator": lambda x, i: x - 1, "site_dependent": lambda x, i: (x - 1.75) * (i + 1) + 0.5 * (x == 1)}[fname]
+    N, E, L, sites, D = bp.g.nv(), bp.g.ne(), bp.T + 1, r["sites"], r["D"]
+    qn = [int(v) for v in bp.qnode]
+    sd = lambda p: np.sqrt(np.maximum(p * (1 - p), 0.0) / n)      # n: the count drawn, not the ESS
+    assert sms.nsamples == n
+    # marginals, pair marginals: the device's numbers, cut to the node's states
+    m, me = M.marginals(sms)
+    for i in range(N):
+        for t in range(L):
+            assert np.array_equal(m[i][t], dev.node[i, t, :qn[i]])
+            _close(me[i][t], sd(dev.node[i, t, :qn[i]]), 1.0)
+    pm, pe = M.pair_marginals(sms)
+    for e in range(E):
+        i, j = bp._ends[e]
+        for t in range(L):
+            assert np.array_equal(pm[e][t], dev.pair[e, t, :qn[i], :qn[j]])
+            _close(pe[e][t], sd(dev.pair[e, t, :qn[i], :qn[j]]), 1.0)
+    # means
+    fx = [np.array([f(x + 1, i) for x in range(qn[i])], dtype=float) for i in range(N)]
+    F = max(np.abs(v).max() for v in fx)
+    mu = [np.array([np.sum(fx[i] * dev.node[i, t, :qn[i]]) for t in range(L)]) for i in range(N)]
+    s = [np.array([np.sqrt(np.sum((fx[i] * sd(dev.node[i, t, :qn[i]])) ** 2)) for t in range(L)]) for i in range(N)]
+    mv, merr = M.means(f, sms)
+    for i in range(N):
+        _close(mv[i], mu[i], F)
+        _close(merr[i], s[i], F)
+    sub = [sites[-1], 0] if 0 not in sites else [0]
+    mv2, merr2 = M.means(f, sms, sites=sub)
+    for a, i in enumerate(sub):
+        _close(mv2[a], mu[i], F)
+        _close(merr2[a], s[i], F)
+    # autocorrelations and autocovariances: the sampler's own window, then a smaller one (where there is one), the
+    # sites reordered, and a subset
+    for want_sites, md in ((None, None), (sorted(sites), None), (sites[:1], None), (sorted(sites), 1)):
+        d = D if md is None else md
+        ss = sites if want_sites is None else want_sites
+        rr, re = M.autocorrelations(f, sms, sites=want_sites, maxdist=md)
+        cv, ce = M.autocovariances(f, sms, sites=want_sites, maxdist=md)
+        assert len(rr) == len(re) == len(cv) == len(ce) == len(ss)
+        for a, i in enumerate(ss):
+            k = sites.index(i)
+            ff = np.outer(fx[i], fx[i])
+            r0, e0 = np.zeros((L, L)), np.zeros((L, L))
+            for t in range(L):
+                for u in range(t + 1, min(L, t + d + 1)):
+                    p = dev.corr[k, t, u, :qn[i], :qn[i]]
+                    r0[t, u] = np.sum(ff * p)
+                    e0[t, u] = np.sqrt(np.sum((ff * sd(p)) ** 2))
+            t, u = np.indices((L, L))
+            outside = ~((t < u) & (u <= t + d))
+            assert np.all(rr[a][outside] == 0.0) and np.all(re[a][outside] == 0.0)
+            _close(rr[a], r0, F * F)
+            _close(re[a], e0, F * F)
+            # covariance(r, mu) = r - mu mu' over the whole matrix; first-order errors
+            c0 = r0 - np.outer(mu[i], mu[i])
+            ce0 = np.sqrt(e0 ** 2 + np.outer(s[i], mu[i]) ** 2 + np.outer(mu[i], s[i]) ** 2)
+            ce0[np.diag_indices(L)] = 2 * np.abs(mu[i]) * s[i]
+            _close(cv[a], c0, F * F)
+            _close(ce[a], ce0, F * F)
+    # the two-time joints the Python layer hands out: None outside the window
+    tv = M.sampling.twovar_marginals(sms)
+    for k in range(len(sites)):
+        for t in range(L):
+            for u in range(L):
+                if t < u <= t + D:
+                    assert np.array_equal(tv[k][t][u], dev.corr[k, t, u])
+                else:
+                    assert tv[k][t][u] is None
+    # effective sample size against the reference's log ESS
+    tess = _tolerances(n, ref)[3]
+    assert abs(np.log(M.effective_sample_size(sms)) - ref.log_ess) <= tess + 4 * U * abs(ref.log_ess)
