@@ -126,6 +126,32 @@ def test_batched_gauge_sweep_matches_oracle(mode, monkeypatch):
     assert np.array_equal(bp.bonds(), np.array([m.bonds for m in obp.mu]))
 
 
+@pytest.mark.parametrize("mode,trunc,damp", [("grid", "TruncBond", 0.0), ("grid_colstep", "TruncBond", 0.0), ("grid", "TruncBondMax", 0.3)])
+def test_batched_truncating_sweep_matches_oracle(mode, trunc, damp, monkeypatch):
+    """The same loopy case with BOTH sweeps of every cavity product on the grid (MPBP_GAUGE=grid, MPBP_SWEEP2=grid): the
+    truncating sweep's descriptors, QR of M_t and Jacobi at a size where it is otherwise never chosen.  TruncBondMax is the
+    other plannable truncation; damping sends its compression against the identity through the same path."""
+    monkeypatch.setenv("MPBP_GAUGE", "grid")
+    monkeypatch.setenv("MPBP_SWEEP2", "grid")
+    monkeypatch.setenv("MPBP_DEBUG_NO_SMALL", "1")
+    if mode == "grid_colstep":
+        monkeypatch.setenv("MPBP_DEBUG_FORCE_TALL", "1")
+    N, T, Mb = 8, 6, 6
+    lam, rho, gam = 0.15, 0.1, 0.2
+    A, phi = _loopy(N, T, lam, rho, gam)
+    bp = M.mpbp(M.IndexedBiDiGraph(A), [[M.SISFactor(lam, rho)] * (T + 1)] * N, 2, T, phi=phi, max_bond=Mb)
+    obp = O.mpbp(O.IndexedBiDiGraph(A), [[OF.SISFactor(lam, rho)] * (T + 1)] * N, [2] * N, T, phi=phi)
+    tr, otr = getattr(M, trunc)(Mb), getattr(OT, trunc)(Mb)
+    for s in range(3):
+        M.iterate(bp, maxiter=1, svd_trunc=tr, tol=0.0, damp=damp)
+        O.iterate(obp, maxiter=1, svd_trunc=otr, tol=0.0, shuffle_nodes=False, jacobi=True, damp=damp)
+        assert _rel(_flat(M.beliefs(bp)), _flat(O.beliefs(obp))) < RTOL, f"sweep {s}"
+        st = bp.last_stats
+        assert st.jacobi_not_converged == 0 and st.nan_flag == 0 and st.capacity_flag == 0, f"sweep {s}"
+    assert abs(M.bethe_free_energy(bp) - O.bethe_free_energy(obp)) < RTOL * max(1.0, np.abs(obp.f).sum())
+    assert np.array_equal(bp.bonds(), np.array([m.bonds for m in obp.mu]))
+
+
 def _fnodes(bp):
     import ctypes as C
     f = np.zeros(bp.g.nv())
