@@ -280,6 +280,46 @@ int mpbp_sampler_counts(mpbp_sampler* s, int64_t* nsamples, double* log_sum_w, d
 /* the sampler's Philox4x32-10 block function on the host (known-answer checks): out = philox(counter[4], key[2]) */
 int mpbp_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
+/*
+ * Exact solvers (reference src/exact.jl): the ground truth MPBP is compared against.  A solver reads the context's CURRENT
+ * factors, node states, phi and psi at every solve (it refreshes when they change) and must be destroyed before its
+ * context.  Both methods start from one dense table per node and time block, W_i^t[x' + q (x_i + q (x_1 + q (x_2 + ...)))]:
+ * the table of a generic factor as it was set, the tables of a recursive factor folded in the order of the sampler's draw.
+ *   method 0, joint enumeration (src/exact.jl:5-41): p of all Q = prod_i q_i^(T+1) trajectories.  p is a C-ordered array of
+ *     shape [q_0]*(T+1) + [q_1]*(T+1) + ... - node-major, time inside, the last node's last time fastest.  log phi^t
+ *     (t = 0 included, src/exact.jl:18), log w, 1/2 log psi per directed edge and, on chains periodic in time, the closing
+ *     factor w[i][T](x^0 | x_nbrs^T, x^T) (src/exact.jl:24-26).  A configuration excluded by a hard observation has p
+ *     exactly 0.  Limits: Q <= 2^32, N (T+1) <= 64, 8 Q bytes plus scratch within the free device memory (MPBP_ENOMEM).
+ *   method 1, global-state forward-backward: the S = prod_i q_i joint states of all nodes at one time (last node fastest),
+ *     a_0 = g_0, a_{t+1} = g_{t+1} (a_t K_t), b_T = 1, b_t = K_t (g_{t+1} b_{t+1}) with g_t = prod phi^t prod psi^t and
+ *     K_t(s -> s') = prod_i W_i^t(s'_i | s), every step normalised.  Exact on any graph at any T, cost T S^2.  Limits:
+ *     S <= 2^16; not on chains periodic in time.  It delivers log Z, marginals and pair marginals only.
+ * Refused at create with MPBP_EUNSUPPORTED: aliased graphs (InfiniteRegularGraph), q > 4, sizes over the limits.  All
+ * sums run in a fixed order: two solves give bit-identical results.  Z = 0 (the observations exclude every trajectory)
+ * is MPBP_EINVAL.
+ */
+typedef struct mpbp_exact mpbp_exact;
+int mpbp_exact_create(mpbp_exact** out, mpbp_ctx* ctx, int32_t method);
+void mpbp_exact_destroy(mpbp_exact* x);
+/* `exact_prob(bp)` (src/exact.jl:5-41) up to the download, or the forward-backward pass; logZ may be NULL */
+int mpbp_exact_solve(mpbp_exact* x, double* logZ);
+/* `exact_marginals(bp)` (src/exact.jl:60-74), layout of mpbp_beliefs, padding states exactly 0 */
+int mpbp_exact_marginals(mpbp_exact* x, double* out);
+/* `exact_pair_marginals(bp)` (src/exact.jl:102-119) per directed edge, layout of mpbp_pair_beliefs (x_src fastest) */
+int mpbp_exact_pair_marginals(mpbp_exact* x, double* out);
+/* method 0 only - the others return MPBP_EUNSUPPORTED on a method 1 solver.  p of `exact_prob(bp)` (src/exact.jl:36-40):
+ * Q doubles in the layout above */
+int mpbp_exact_prob(mpbp_exact* x, double* p);
+/* loads a p computed earlier (the `p` / `p_exact` keyword of src/exact.jl:43,60,85,102,132,161): the reductions below and
+ * the two marginals above then run on it until the next solve */
+int mpbp_exact_set_prob(mpbp_exact* x, const double* p);
+/* `site_marginals(bp; p)` (src/exact.jl:43-58): the marginal of the whole trajectory of `node`, q_i^(T+1) doubles,
+ * C-ordered [q_i]*(T+1) (last time fastest) */
+int mpbp_exact_site_marginals(mpbp_exact* x, int32_t node, double* out);
+/* the exact `pair_marginals(bp; p)` (src/exact.jl:85-100): the joint of the two trajectories of edge i -> j,
+ * q_i^(T+1) q_j^(T+1) doubles, C-ordered [traj_i][traj_j] whichever of i, j is the larger */
+int mpbp_exact_edge_marginals(mpbp_exact* x, int32_t edge, double* out);
+
 /* Self-test entry points used by tests/ (device building blocks against host references). */
 int mpbp_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const double* A, const double* B,
                        double* C);

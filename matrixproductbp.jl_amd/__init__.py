@@ -12,5 +12,8 @@ from .mpbp import (CB_BP, MPBP, random_message, periodic_mpbp, periodic_mpbp_inf
                    onebpiter, pair_beliefs, reset_messages, pair_beliefs_as_mpem, pair_correlations,
                    alternate_marginals, alternate_correlations, expectation, logprob, reset, reset_observations,
                    is_free_dynamics)
+from .exact import (ExactSolver, exact_alternate_marginal_expectations, exact_alternate_marginals, exact_autocorrelations,
+                    exact_autocovariances, exact_marginal_expectations, exact_marginals, exact_pair_marginal_expectations,
+                    exact_pair_marginals, exact_prob, site_marginals)
 from .sampling import (SoftMarginSampler, draw_node_observations, effective_sample_size, marginals, mean_with_uncertainty,
                        onesample, pair_marginals, sample)

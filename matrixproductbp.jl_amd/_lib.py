@@ -9,7 +9,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libmpbp_hip.so")
-SOURCES = ["mpbp_hip.hip", "v2_engine.hip", "sampler.hip"]
+SOURCES = ["mpbp_hip.hip", "v2_engine.hip", "sampler.hip", "exact.hip"]
 
 
 def headers():
@@ -58,7 +58,9 @@ EXPORTS = ["mpbp_create", "mpbp_destroy", "mpbp_last_error", "mpbp_slab_layout",
            "mpbp_free_energy", "mpbp_logz", "mpbp_allgather_slots", "mpbp_twovar_marginals", "mpbp_set_profiling", "mpbp_phase_profile", "mpbp_selftest_gemm", "mpbp_selftest_qr", "mpbp_selftest_qr_bench",
            "mpbp_selftest_jacobi_bench", "mpbp_selftest_svd", "mpbp_selftest_qr_batched", "mpbp_selftest_qr_batched_seq", "mpbp_selftest_jacobi_grid", "mpbp_selftest_jacobi_block",
            "mpbp_sampler_create", "mpbp_sampler_destroy", "mpbp_sample", "mpbp_sampler_marginals",
-           "mpbp_sampler_pair_marginals", "mpbp_sampler_twovar_marginals", "mpbp_sampler_counts", "mpbp_philox4x32_10"]
+           "mpbp_sampler_pair_marginals", "mpbp_sampler_twovar_marginals", "mpbp_sampler_counts", "mpbp_philox4x32_10",
+           "mpbp_exact_create", "mpbp_exact_destroy", "mpbp_exact_solve", "mpbp_exact_marginals", "mpbp_exact_pair_marginals",
+           "mpbp_exact_prob", "mpbp_exact_set_prob", "mpbp_exact_site_marginals", "mpbp_exact_edge_marginals"]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -154,6 +156,16 @@ def lib():
     L.mpbp_sampler_twovar_marginals.argtypes = [C.c_void_p, dp]
     L.mpbp_sampler_counts.argtypes = [C.c_void_p, lp, dp, dp]
     L.mpbp_philox4x32_10.argtypes = [u32p, u32p, u32p]
+    L.mpbp_exact_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int32]
+    L.mpbp_exact_destroy.argtypes = [C.c_void_p]
+    L.mpbp_exact_destroy.restype = None
+    L.mpbp_exact_solve.argtypes = [C.c_void_p, dp]
+    L.mpbp_exact_marginals.argtypes = [C.c_void_p, dp]
+    L.mpbp_exact_pair_marginals.argtypes = [C.c_void_p, dp]
+    L.mpbp_exact_prob.argtypes = [C.c_void_p, dp]
+    L.mpbp_exact_set_prob.argtypes = [C.c_void_p, dp]
+    L.mpbp_exact_site_marginals.argtypes = [C.c_void_p, C.c_int32, dp]
+    L.mpbp_exact_edge_marginals.argtypes = [C.c_void_p, C.c_int32, dp]
     _lib = L
     return L
 
