@@ -320,6 +320,67 @@ int mpbp_exact_site_marginals(mpbp_exact* x, int32_t node, double* out);
  * q_i^(T+1) q_j^(T+1) doubles, C-ordered [traj_i][traj_j] whichever of i, j is the larger */
 int mpbp_exact_edge_marginals(mpbp_exact* x, int32_t edge, double* out);
 
+/*
+ * Population dynamics for the equilibrium magnetisation of the Ising model on infinite diluted graphs (reference
+ * src/Models/glauber/equilibrium.jl:72-127, `equilibrium_magnetization`): the steady state a long Glauber run is compared
+ * against.  A handle owns two device arrays of popsize cavity fields, old and new.  One sweep is synchronous - member i
+ * of the new array is computed from the old array only (src/Models/glauber/equilibrium.jl:91-100):
+ *   km1 ~ pkm1;  h ~ ph;  for n = 0..km1-1:  a_n = min(floor(u popsize), popsize - 1),  J_n ~ pJ
+ *   P_new[i] = (1/beta) (sum_n atanh(tanh(beta P_old[a_n]) tanh(beta J_n))) + h
+ * in fp64 with contraction off, the sum started at 0.0 and taken in the order n = 0, 1, ..., (1/beta) rounded once; km1 = 0
+ * gives exactly h.  Then the arrays are swapped.
+ * Random numbers: Philox4x32-10 (the block function of mpbp_philox4x32_10), key = (seed lo, seed hi) and
+ *   counter = (member, slot, sweep, phase)
+ *     phase 0: the sweeps; sweep = 1, 2, ... counted over the handle's lifetime; member = index in the population
+ *     phase 1: the final draw; sweep = 1, 2, ... the number of the mpbp_popdyn_magnetization call; member = sample index
+ * One block r[0..3] yields two uniforms in [0, 1):
+ *   uA = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53,   uB = ((r2 >> 5) 2^26 + (r3 >> 6)) 2^-53
+ *     slot 0       uA        -> degree
+ *     slot 1       (uA, uB)  -> field h
+ *     slot 2 + 2n  uA        -> index a_n
+ *     slot 3 + 2n  (uA, uB)  -> coupling J_n
+ * A draw is a function of (seed, phase, sweep, member, slot) only: not of the launch geometry, not of how the caller
+ * splits mpbp_popdyn_iterate calls.
+ * Distributions are tables (kind, n, values[n], cdf[n]) computed on the host and used verbatim on the device:
+ *   MPBP_POPDYN_DIRAC     n = 1: values[0] (cdf is not read)
+ *   MPBP_POPDYN_DISCRETE  1 <= n <= 256: values[j] of the first j with cdf[j] > uA, the last entry if there is none;
+ *                         cdf finite, non-negative and non-decreasing
+ *   MPBP_POPDYN_NORMAL    n = 2, values = (mu, sigma): mu + sigma * sqrt(-2 log(1 - uA)) * cos(6.283185307179586 * uB),
+ *                         the products taken left to right (cdf is not read; 1 - uA is never 0)
+ * Degrees (pkm1, pk) are DIRAC or DISCRETE with integer values in 0..2^20.
+ * The mean of a sweep is a deterministic function of the new population alone: members are grouped in blocks of 256
+ * (0.0 beyond popsize), each block reduced by the tree `for s = 128, 64, .., 1: x[t] += x[t + s] for t < s`; then x[t] =
+ * the sum, started at 0.0, of the block sums t, t + 256, t + 512, ... in that order, the same tree over x, and x[0] / popsize.
+ * Deliberate differences from the reference: it updates one array in place in shuffled order and alternates between two
+ * arrays (same fixed-point distribution, another trajectory towards it); it draws from Julia's GLOBAL_RNG, here draws are
+ * counter based and reproducible; it accepts any `Distribution`, here only the kinds above (the host tabulates Poisson
+ * as DISCRETE); `equilibrium_energy` (src/Models/glauber/equilibrium.jl:37-40) refers to undefined names there and is
+ * not ported.  There is no context: after a failure the message is read through mpbp_last_error(NULL), and the handle
+ * stays usable.
+ */
+typedef struct mpbp_popdyn mpbp_popdyn;
+enum { MPBP_POPDYN_DIRAC = 0, MPBP_POPDYN_DISCRETE = 1, MPBP_POPDYN_NORMAL = 2 };
+enum { MPBP_POPDYN_PKM1 = 0, MPBP_POPDYN_PK = 1, MPBP_POPDYN_PJ = 2, MPBP_POPDYN_PH = 3 };
+/* `P = randn(rng, popsize)`, `Pnew = copy(P)` (src/Models/glauber/equilibrium.jl:86-89).  P0: popsize doubles on the
+ * host, NULL for zeros.  popsize outside 1..2^31-1, beta <= 0 or not finite: MPBP_EINVAL; a failed allocation: MPBP_ENOMEM. */
+int mpbp_popdyn_create(mpbp_popdyn** out, int32_t device, int64_t popsize, uint64_t seed, double beta, const double* P0);
+void mpbp_popdyn_destroy(mpbp_popdyn* p);
+/* the keywords `pkm1`, `pk`, `pJ`, `ph` (src/Models/glauber/equilibrium.jl:82-84); `which` is MPBP_POPDYN_PKM1..PH.  A table
+ * that breaks the rules above is MPBP_EINVAL and leaves the previous one in place. */
+int mpbp_popdyn_set_distribution(mpbp_popdyn* p, int32_t which, int32_t kind, int32_t n, const double* values,
+                                 const double* cdf);
+/* nsweeps times `iterate_bp!` (src/Models/glauber/equilibrium.jl:93-100, 106), queued without a host synchronisation
+ * between sweeps; mean_after_each: host [nsweeps], the mean of the population after each sweep (the default statistic of
+ * `CB_Pop`, :61-62), may be NULL.  nsweeps < 1, or pkm1 / pJ / ph not set: MPBP_EINVAL. */
+int mpbp_popdyn_iterate(mpbp_popdyn* p, int32_t nsweeps, double* mean_after_each);
+/* the current population, popsize doubles */
+int mpbp_popdyn_get_population(mpbp_popdyn* p, double* P);
+int mpbp_popdyn_set_population(mpbp_popdyn* p, const double* P);
+/* the final draw (src/Models/glauber/equilibrium.jl:115-121): m[s] = tanh(beta f) with degree ~ pk from the current
+ * population, s = 0..nsamples-1; mean and standard error are left to the host.  nsamples outside 1..2^31-1, or pk / pJ /
+ * ph not set: MPBP_EINVAL. */
+int mpbp_popdyn_magnetization(mpbp_popdyn* p, int64_t nsamples, double* m);
+
 /* Self-test entry points used by tests/ (device building blocks against host references). */
 int mpbp_selftest_gemm(int32_t device, int32_t M, int32_t N, int32_t K, const double* A, const double* B,
                        double* C);

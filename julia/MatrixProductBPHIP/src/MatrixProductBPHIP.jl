@@ -243,4 +243,63 @@ rank's `mpbp_sweep` visible on all ranks - the `bp.μ[idx(e)] = μj` of src/recu
 allgather_slots!(be::HIPBackend, comm::Ptr{Cvoid}, rank::Integer, world::Integer, S::Integer) =
     check(ccall((:mpbp_allgather_slots, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32), be.h, comm, rank, world, S), be.h)
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Population dynamics of src/Models/glauber/equilibrium.jl:72-127 on the device (mpbp_popdyn_* of include/mpbp_hip.h).
+# No context is involved: messages of failed calls come from mpbp_last_error(NULL), which `check(rc)` reads.
+
+"A population of cavity fields on the device.  `P0`: the initial population (`randn(rng, popsize)` in the reference)."
+mutable struct PopDyn
+    h::Ptr{Cvoid}
+    popsize::Int
+    function PopDyn(P0::Vector{Float64}; β::Real=1.0, seed::Integer=0, device::Integer=0)
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:mpbp_popdyn_create, LIB), Cint, (Ref{Ptr{Cvoid}}, Int32, Int64, UInt64, Float64, Ptr{Float64}),
+                    h, device, length(P0), seed % UInt64, β, P0))
+        p = new(h[], length(P0))
+        finalizer(q -> ccall((:mpbp_popdyn_destroy, LIB), Cvoid, (Ptr{Cvoid},), q.h), p)
+    end
+end
+
+const POPDYN_PKM1, POPDYN_PK, POPDYN_PJ, POPDYN_PH = Int32(0), Int32(1), Int32(2), Int32(3)
+
+"Table (kind, values, cdf) of a distribution in the form `mpbp_popdyn_set_distribution` takes; `vals`/`probs` describe a
+ discrete law (for `Poisson(c)`: 0:K with K the first k whose upper tail is below 2^-53, at most 256 entries)."
+popdyn_table(v::Real) = (Int32(0), Float64[v], Float64[])                          # Dirac(v)
+popdyn_table(μ::Real, σ::Real) = (Int32(2), Float64[μ, σ], Float64[])              # Normal(μ, σ)
+function popdyn_table(vals::AbstractVector{<:Real}, probs::AbstractVector{<:Real})
+    cdf = min.(cumsum(Float64.(probs)), 1.0); cdf[end] = 1.0
+    (Int32(1), Float64.(vals), cdf)
+end
+
+function set_distribution!(p::PopDyn, which::Integer, tab)
+    kind, values, cdf = tab
+    check(ccall((:mpbp_popdyn_set_distribution, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                p.h, which, kind, length(values), values, isempty(cdf) ? C_NULL : cdf))
+end
+
+"`nsweeps` synchronous sweeps queued on the device (`iterate_bp!`, equilibrium.jl:93-100); returns the mean after each."
+function iterate_popdyn!(p::PopDyn, nsweeps::Integer)
+    means = zeros(Float64, nsweeps)
+    check(ccall((:mpbp_popdyn_iterate, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.h, nsweeps, means))
+    means
+end
+
+function population(p::PopDyn)
+    P = zeros(Float64, p.popsize)
+    check(ccall((:mpbp_popdyn_get_population, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.h, P))
+    P
+end
+
+function set_population!(p::PopDyn, P::Vector{Float64})
+    length(P) == p.popsize || error("set_population!: expected $(p.popsize) values")
+    check(ccall((:mpbp_popdyn_set_population, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.h, P))
+end
+
+"The final draw (equilibrium.jl:115-121): `nsamples` values of tanh(β f) from the current population."
+function magnetization_samples(p::PopDyn, nsamples::Integer)
+    m = zeros(Float64, nsamples)
+    check(ccall((:mpbp_popdyn_magnetization, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}), p.h, nsamples, m))
+    m
+end
+
 end # module
