@@ -62,6 +62,43 @@ __device__ inline void build_E(DP E, DP A2c, const gdbl* pyy, int b, int bn, int
   }
 }
 
+// ---- the structural zeros of a gauge factor.  Lf_{t+1}^T [r1 x Bn] (rank index k fastest, m = n1 + an*n2) is the R of a QR, upper
+// trapezoidal, and both writers of it (sweep 1 below, k_lf_write of the batched sweep) store the zeros.  THE zero set:
+__device__ __forceinline__ bool lf_zero(int k, int m) { return m < k; }
+// Z[(k,n2) ; .] = sum_n1 A1[., n1, .] Lf^T[k, n1 + an*n2] is zero when the whole run n1 < an is, i.e. when its last column
+// an*(n2+1) - 1 is:  an*(n2+1) <= k.  RULE: no lane ever uses a Z value of this set, written or not - Y1 does not write the output
+// tiles that lie wholly inside it, and the slot's Z region then still holds numbers of an earlier problem there.
+__device__ __forceinline__ int z_run_end(int an, int n2) { return an * (n2 + 1) - 1; }
+__device__ __forceinline__ bool z_zero(int an, int k, int n2) { return lf_zero(k, z_run_end(an, n2)); }
+// The three products that multiply by these zeros, as zero policies of the GEMMs (wg_blocks.h: keys xm of the contraction index
+// and xk of the column, z(xk, xm) = "X(kk, j) is a known zero").
+//   Y1:  X(n1, j = k + r1*n2) = Lf^T[k, n1 + an*n2]: both indices counted from the start an*n2 of the run.  A tile is skipped when
+//        its 16 columns are zero at n1 = an - 1, which is z_zero(an, k, n2) for each of them.
+struct LfZeroY1 {
+  static constexpr bool on = true, skip_tiles = true, skip_ksteps = false;
+  int an, r1;
+  __device__ __forceinline__ int xm(int n1) const { return n1; }
+  __device__ __forceinline__ int xk(int j) const { return (j % r1) - an * (j / r1); }
+  __device__ __forceinline__ bool z(int xk_, int xm_) const { return lf_zero(xk_, xm_); }
+};
+//   Y2:  X(kk = n2 + bn*y1, j = k + r1*m1) = Z[(k,n2) ; (m1,y1,xi)]: z_zero(an, k, n2), with the end of the run as the key of kk
+struct LfZeroY2 {
+  static constexpr bool on = true, skip_tiles = false, skip_ksteps = true;
+  static constexpr int xm_none = -1, xk_none = 0x7fffffff;      // a run that ends at m = -1 < k;  k = INT_MAX > every m
+  int an, bn, r1;
+  __device__ __forceinline__ int xm(int kk) const { return z_run_end(an, kk % bn); }
+  __device__ __forceinline__ int xk(int j) const { return j % r1; }
+  __device__ __forceinline__ bool z(int k, int mend) const { return lf_zero(k, mend); }
+};
+//   M_t: X(m, j = k) = Lf^T[k, m]
+struct LfZeroMt {
+  static constexpr bool on = true, skip_tiles = false, skip_ksteps = true;
+  static constexpr int xm_none = -1, xk_none = 0x7fffffff;
+  __device__ __forceinline__ int xm(int m) const { return m; }
+  __device__ __forceinline__ int xk(int k) const { return k; }
+  __device__ __forceinline__ bool z(int k, int m) const { return lf_zero(k, m); }
+};
+
 __device__ inline void atomic_max_double_pos(unsigned long long* addr, double v) {
   atomicMax(addr, (unsigned long long)__double_as_longlong(v));
 }
@@ -138,7 +175,7 @@ __device__ void run_problem(const EngProb& P, const EngCfg& cfg, double* slot_, 
          [=](int i) { return (i % a) + a * an * (i / a); }, [=](int kk) { return a * kk; },
          Lf1, [=](int kk) { return (int64_t)r1 * kk; },
          [=](int j) { return (int64_t)(j % r1) + (int64_t)r1 * an * (j / r1); },
-         Z, [=](int i) { return zld * i; }, [=](int j) { return (int64_t)j; }, false);
+         Z, [=](int i) { return zld * i; }, [=](int j) { return (int64_t)j; }, false, -1, WG_WAVES, LfZeroY1{an, r1});
     PROF(PH_Y1);
     // Y2 (per xi): Y[(k,y,xi) ; (m1,m2)] = sum_(n2,y1) E_xi[(m2,y),(n2,y1)] Z[(k,n2),(m1,y1,xi)]
     const int rowsY = r1 * ny * q;
@@ -160,7 +197,7 @@ __device__ void run_problem(const EngProb& P, const EngCfg& cfg, double* slot_, 
            [=](int j) { return (int64_t)(j % r1) + zld * (j / r1); },
            Y + (int64_t)r1 * ny * xi,
            [=](int i) { return (int64_t)r1 * (i / b) + (int64_t)ldY * a * (i % b); },
-           [=](int j) { return (int64_t)(j % r1) + (int64_t)ldY * (j / r1); }, false);
+           [=](int j) { return (int64_t)(j % r1) + (int64_t)ldY * (j / r1); }, false, -1, WG_WAVES, LfZeroY2{an, bn, r1});
     }
     PROF(PH_Y2);
     qr_r(Y, ldY, rowsY, Bm, ldsQ, ldsG, pr, &plast, PH_QR1_PANEL, PH_QR1_TRAIL, cfg.force_generic != 0);
@@ -284,7 +321,7 @@ __device__ void run_problem(const EngProb& P, const EngCfg& cfg, double* slot_, 
     //  ceil(Rr / 16) = 5 of the 8 waves of configs[1] had a tile, over five M blocks.)
     gemm(Rr, r1, Bn, Nt, [=](int i) { return (int64_t)i; }, [=](int kk) { return (int64_t)Rr * kk; },
          Lf1, [=](int kk) { return (int64_t)r1 * kk; }, [=](int j) { return j; }, false,
-         Mt, [=](int i) { return (int64_t)ldM * i; }, [=](int j) { return j; }, false, ldsG);
+         Mt, [=](int i) { return (int64_t)ldM * i; }, [=](int j) { return j; }, false, ldsG, LfZeroMt{});
     PROF(PH_MT);
     qr_r(Mt, ldM, r1, Rr, ldsQ, ldsG, pr, &plast, PH_QR2_PANEL, PH_QR2_TRAIL, cfg.force_generic != 0);
     const int k2 = min(r1, Rr);

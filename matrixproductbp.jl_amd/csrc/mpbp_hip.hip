@@ -467,6 +467,7 @@ struct SweepEnv {
   bool force_small = false;     // MPBP_DEBUG_FORCE_SMALL: few single-wave problems stay on the single-wave variant
   bool no_pack = false;         // MPBP_DEBUG_NO_PACK: cavity launches level by level instead of by readiness
   bool coop_fail_once = false;  // MPBP_DEBUG_COOP_FAIL_ONCE: pretend that a batch's first gauge sweep timed out
+  bool poison_z = false;        // MPBP_DEBUG_POISON_Z=1: NaN-fill the Z region of every slot before each engine launch (engine.h, z_zero)
   Form gauge = FORM_AUTO, sweep2 = FORM_AUTO;   // MPBP_GAUGE, MPBP_SWEEP2: force where sweeps 1 and 2 run
 };
 static SweepEnv read_sweep_env() {
@@ -475,7 +476,7 @@ static SweepEnv read_sweep_env() {
   auto form = [](const char* name) { const char* e = getenv(name); return !e ? FORM_AUTO : !strcmp(e, "grid") ? FORM_GRID : !strcmp(e, "wg") ? FORM_WG : FORM_AUTO; };
   const char* split = getenv("MPBP_DEBUG_SPLIT_NODES");
   return SweepEnv{split ? atoi(split) : 0, is1("MPBP_DEBUG_FORCE_GENERIC"), is1("MPBP_DEBUG_NO_SMALL"), set("MPBP_DEBUG_FORCE_SMALL"),
-                  set("MPBP_DEBUG_NO_PACK"), set("MPBP_DEBUG_COOP_FAIL_ONCE"), form("MPBP_GAUGE"), form("MPBP_SWEEP2")};
+                  set("MPBP_DEBUG_NO_PACK"), set("MPBP_DEBUG_COOP_FAIL_ONCE"), is1("MPBP_DEBUG_POISON_Z"), form("MPBP_GAUGE"), form("MPBP_SWEEP2")};
 }
 // what the stages of one pass share: the context, the switches, the truncation and the timers of the cavity launches
 struct Pass {
@@ -629,6 +630,10 @@ static int launch_slots(Pass& ps, const EngLaunchPlan& pl, const EngProb* probs,
   EngProb* d_probs = (EngProb*)(c->scratch.base + (((size_t)nslots * slot_bytes + 255) & ~size_t(255)));
   HIPCHK(c, hipMemcpyAsync(d_probs, probs, sizeof(EngProb) * np, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_counter, 0, sizeof(int), c->stream));
+  // Y1 leaves the tiles of Z that lie wholly in the zero set of Lf unwritten and Y2 must never use them: with the switch they hold NaN
+  // instead of an earlier problem's finite numbers, so that a lane that did use one shows in the result
+  if (ps.env.poison_z)
+    HIPCHK(c, hipMemset2DAsync(d_scr + cfg.off_Z, slot_bytes, 0xFF, (size_t)(cfg.off_Y - cfg.off_Z) * 8, (size_t)nslots, c->stream));
   if (e0) hipEventRecord(e0, c->stream);      // the workgroup form is timed kernel only (host planning excluded)
   hipLaunchKernelGGL(kern, dim3(nslots), dim3(nthreads), lds_bytes, c->stream, d_probs, np, c->d_counter, cfg, d_scr, c->d_stats);
   HIPCHK(c, hipGetLastError());

@@ -27,23 +27,38 @@ constexpr int GM_LDA = 112;  // LDS leading dims: == 16 (mod 32) doubles so that
 constexpr int GM_LDB = 144;  // ds_read_b64 half-wave land on disjoint banks
 constexpr int GM_LDS_DOUBLES = GM_KC * (GM_LDA + GM_LDB);   // 8192 doubles = 64 KiB
 
+// Structural zeros of X, as an optional last argument of both GEMMs.  A policy ZP maps the two indices of X(kk, j) to two keys,
+// xm(kk) and xk(j), and says with z(xk, xm) whether the element is a KNOWN zero.  z must be monotone - z(xk, xm) implies
+// z(xk', xm') for xk' >= xk, xm' <= xm - and so must the keys where a whole range is judged by its end: xm nondecreasing in kk for
+// ZP::skip_tiles and for gemm(), xk nondecreasing in j for gemm().
+//   ZP::skip_tiles   gemm_direct: an output tile whose 16 columns of X are all known zeros is neither computed NOR STORED
+//   ZP::skip_ksteps  gemm_direct: a k-step whose 4 x 16 elements are all known zeros does not read them - its load goes, all lanes
+//                    alike, to the first element of X, one line that stays in the cache - and every lane takes 0.0 for a known zero
+//                    whatever memory holds there.  The load is redirected and not skipped, and the MFMAs still run, on zeros,
+//                    because the software pipeline needs a fixed number of loads in flight and a straight-line MFMA block: with
+//                    a branch per k-step the compiler waits for ALL loads before the first MFMA (measured).
+//                    Needs two keys that are zero against everything: ZP::xm_none (for kk outside K), ZP::xk_none (j outside N).
+//   gemm():          the leading K chunks that are known zeros for every column of the current N chunk are not staged
+// The default says that nothing is zero, and every `if constexpr` below then leaves the code as it is without a policy.
+struct NoZeros { static constexpr bool on = false, skip_tiles = false, skip_ksteps = false; };
+
 template <bool NTX = false, bool NTO = false, class SP, class XP, class OP, class SRO, class SCO, class XRO, class XCO,
-          class ORO, class OCO>
+          class ORO, class OCO, class ZP = NoZeros>
 __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp, SRO sro, SCO sco,
                                                      XP Xp, XRO xro, XCO xco, OP Op, ORO oro, OCO oco,
-                                                     bool accumulate, int tile0 = -1, int tstride = WG_WAVES);
+                                                     bool accumulate, int tile0 = -1, int tstride = WG_WAVES, ZP zp = ZP{});
 
 // O(i,j) (+)= sum_k S(i,k) X(k,j),  i<M, j<N, k<K.
 //   S(i,k) = Sp[sro(i) + sco(k)],  X(k,j) = Xp[xro(k) + xco(j)],  O(i,j) = Op[oro(i) + oco(j)].
 // `xkfast`: X is contiguous along k (else along j) - only picks the coalesced staging pattern.
 // `lds` must provide GM_LDS_DOUBLES doubles.  Ends with a __syncthreads().
-template <class SRO, class SCO, class XRO, class XCO, class ORO, class OCO>
+template <class SRO, class SCO, class XRO, class XCO, class ORO, class OCO, class ZP = NoZeros>
 __device__ __attribute__((noinline)) void gemm(int M, int N, int K, const gdbl* Sp, SRO sro, SCO sco, const gdbl* Xp, XRO xro,
-                     XCO xco, bool xkfast, gdbl* Op, ORO oro, OCO oco, bool accumulate, ldbl* lds) {
+                     XCO xco, bool xkfast, gdbl* Op, ORO oro, OCO oco, bool accumulate, ldbl* lds, ZP zp = ZP{}) {
 #if WG_THREADS != 512
   // the LDS staging maps below are laid out for 512 threads; smaller workgroups take the barrier-free form
   (void)xkfast; (void)lds;
-  gemm_direct<false, false>(M, N, K, Sp, sro, sco, Xp, xro, xco, Op, oro, oco, accumulate);
+  gemm_direct<false, false>(M, N, K, Sp, sro, sco, Xp, xro, xco, Op, oro, oco, accumulate, -1, WG_WAVES, zp);
 #else
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -111,8 +126,14 @@ __device__ __attribute__((noinline)) void gemm(int M, int N, int K, const gdbl* 
           }
         }
       };
-      load_chunk(0);
-      for (int k0 = 0; k0 < K; k0 += GM_KC) {
+      // first K chunk that is not all known zeros for the columns >= n0 (workgroup-uniform: every wave passes the same barriers)
+      int kbeg = 0;
+      if constexpr (ZP::on) {
+        const int xk0 = zp.xk(n0);
+        while (kbeg < K && zp.z(xk0, zp.xm(min(kbeg + GM_KC, K) - 1))) kbeg += GM_KC;
+      }
+      load_chunk(kbeg);
+      for (int k0 = kbeg; k0 < K; k0 += GM_KC) {
         // ---- stage the S tile As[kk][i] and the X tile Bs[kk][j] from the registers
         if (s_act) {
 #pragma unroll
@@ -178,10 +199,10 @@ __device__ __attribute__((noinline)) void gemm(int M, int N, int K, const gdbl* 
 // each other.  Same index-map interface as gemm().  Ends with a __syncthreads().
 // SP / XP / OP are address-space typed pointers (ldbl* or gdbl*, see wg_common.h).  NTX / NTO: nontemporal loads of
 // X / stores of O - for streams far larger than the caches that would only evict the operands that are reused.
-template <bool NTX, bool NTO, class SP, class XP, class OP, class SRO, class SCO, class XRO, class XCO, class ORO, class OCO>
+template <bool NTX, bool NTO, class SP, class XP, class OP, class SRO, class SCO, class XRO, class XCO, class ORO, class OCO, class ZP>
 __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp, SRO sro, SCO sco,
                                                      XP Xp, XRO xro, XCO xco, OP Op, ORO oro, OCO oco,
-                                                     bool accumulate, int tile0, int tstride) {
+                                                     bool accumulate, int tile0, int tstride, ZP zp) {
   // tile0 / tstride: first 16-column output tile of this wave and the stride to its next one (defaults: the waves of
   // ONE workgroup share the tiles; the grid-level contractions of the batched sweep pass global wave numbers)
   const int tid = threadIdx.x;
@@ -189,6 +210,20 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
   const int g = lane >> 4, l15 = lane & 15;
   const int nks = (K + 3) >> 2;
   const int ntile = (N + 15) >> 4;
+  constexpr bool ZT = ZP::on && ZP::skip_tiles, ZK = ZP::on && ZP::skip_ksteps;
+  // ZT: the wave's first tile at or after tl that has a column with an X element outside the zero set (the last contraction
+  // index carries the largest key).  Wave-uniform: the ballot is over the tile's 16 columns.
+  auto live_tile = [&](int tl) {
+    if constexpr (ZT) {
+      const int xm_last = zp.xm(K - 1);
+      while (tl < ntile) {
+        const int j = tl * 16 + l15;
+        if (__ballot(j < N && !zp.z(zp.xk(j < N ? j : 0), xm_last)) != 0) break;
+        tl += tstride;
+      }
+    }
+    return tl;
+  };
   for (int mb = 0; mb < M; mb += GM_MB) {
     const int mrows = min(GM_MB, M - mb);
     const int ntm = (mrows + 15) >> 4;
@@ -203,17 +238,28 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
     // Software pipeline over (tile, group of 5 k-steps): the X loads of the next group - of this tile or of the
     // wave's next tile - are issued before the MFMAs of the current one.  (Measured at low occupancy these
     // contractions are latency bound, not bandwidth bound.)
+    // ZK: `kin` is the lane's mask of the elements it may use - inside K and N and outside the zero set, for the tile whose
+    // column key is xk.  A k-step in which no lane has one loads X[0] instead.
     struct Grp { double b[5]; long so[5]; unsigned kin; };
-    auto fetch = [&](long cofs, int ks0, Grp& G) {
+    auto fetch = [&](long cofs, int ks0, Grp& G, int xk, bool jn) {
       G.kin = 0;
 #pragma unroll
       for (int u = 0; u < 5; u++) {
         const int k = 4 * (ks0 + u) + g;
         const bool kin = (ks0 + u < nks) && k < K;
         const int kc = kin ? k : 0;
-        G.b[u] = NTX ? __builtin_nontemporal_load(Xp + ((long)xro(kc) + cofs)) : Xp[(long)xro(kc) + cofs];   // valid address, masked later
-        G.so[u] = (long)sco(kc);
-        G.kin |= kin ? (1u << u) : 0u;
+        if constexpr (ZK) {
+          const bool use = kin && jn && !zp.z(xk, zp.xm(kc));
+          G.kin |= use ? (1u << u) : 0u;
+          long o = (long)xro(kc) + cofs;
+          if (__ballot(use) == 0) o = 0;                                 // wave-uniform select, no branch
+          G.b[u] = NTX ? __builtin_nontemporal_load(Xp + o) : Xp[o];
+          G.so[u] = (long)sco(kc);
+        } else {
+          G.b[u] = NTX ? __builtin_nontemporal_load(Xp + ((long)xro(kc) + cofs)) : Xp[(long)xro(kc) + cofs];   // valid address, masked later
+          G.so[u] = (long)sco(kc);
+          G.kin |= kin ? (1u << u) : 0u;
+        }
       }
     };
     // The tile loop with the number of 16-row tiles of this M block a compile-time constant: as a run-time bound every (tile, k-step)
@@ -223,28 +269,34 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
     // clamped, valid address there).
     auto tiles = [&](auto ntm_c) {
       constexpr int NTM = decltype(ntm_c)::value;
-      int tl = tile0 < 0 ? wave : tile0;
+      int tl = live_tile(tile0 < 0 ? wave : tile0);
       if (tl >= ntile) return;
       int j = tl * 16 + l15;
       bool jin = j < N;
       long cofs = jin ? (long)xco(j) : 0;
+      int xk = 0, xk2 = 0;                                              // column keys of this tile and of the next (ZK)
+      if constexpr (ZK) xk = zp.xk(jin ? j : 0);
       Grp cur, nxt;
-      fetch(cofs, 0, cur);
+      fetch(cofs, 0, cur, xk, jin);
       for (;;) {
         d4 acc[NTM];
 #pragma unroll
         for (int t = 0; t < NTM; t++) acc[t] = d4{0, 0, 0, 0};
-        const int tl2 = tl + tstride;
+        const int tl2 = live_tile(tl + tstride);                        // the prefetch below is for the next tile that is computed
         const int j2 = tl2 * 16 + l15;
         const bool jin2 = j2 < N;
         long cofs2 = 0;
         for (int ks0 = 0; ks0 < nks; ks0 += 5) {
-          if (ks0 + 5 < nks) fetch(cofs, ks0 + 5, nxt);                 // wave-uniform branches
-          else if (tl2 < ntile) { cofs2 = jin2 ? (long)xco(j2) : 0; fetch(cofs2, 0, nxt); }
+          if (ks0 + 5 < nks) fetch(cofs, ks0 + 5, nxt, xk, jin);        // wave-uniform branches
+          else if (tl2 < ntile) {
+            cofs2 = jin2 ? (long)xco(j2) : 0;
+            if constexpr (ZK) xk2 = zp.xk(jin2 ? j2 : 0);
+            fetch(cofs2, 0, nxt, xk2, jin2);
+          }
 #pragma unroll
           for (int u = 0; u < 5; u++) {
             const bool kin = (cur.kin >> u) & 1u;
-            const double bv = (kin && jin) ? cur.b[u] : 0.0;
+            const double bv = (kin && (ZK || jin)) ? cur.b[u] : 0.0;    // ZK: kin holds jin and the zero set as well
 #pragma unroll
             for (int t = 0; t < NTM; t++) acc[t] = mfma(Sp[s_ro[t] + cur.so[u]], bv, acc[t]);
           }
@@ -268,7 +320,7 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
         }
         tl = tl2;
         if (tl >= ntile) break;
-        j = j2; jin = jin2; cofs = cofs2;
+        j = j2; jin = jin2; cofs = cofs2; xk = xk2;
       }
     };
     // K <= 40 (every contraction of configs[1]): the k-dependent parts of the index maps - integer divisions by run-time bond
@@ -278,6 +330,7 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
     if (nks <= 5 * NGC) {
       long xr_[NGC][5], so_[NGC][5];
       unsigned kinm[NGC];
+      int xm_[NGC][5];                                                  // ZK: the lane's contraction keys, as tile independent as xr_
 #pragma unroll
       for (int gi = 0; gi < NGC; gi++) {
         kinm[gi] = 0;
@@ -289,41 +342,56 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
           xr_[gi][u] = (long)xro(kc);
           so_[gi][u] = (long)sco(kc);
           kinm[gi] |= kin ? (1u << u) : 0u;
+          if constexpr (ZK) xm_[gi][u] = kin ? zp.xm(kc) : ZP::xm_none;
         }
       }
       auto tiles_c = [&](auto ntm_c) {
         constexpr int NTM = decltype(ntm_c)::value;
-        int tl = tile0 < 0 ? wave : tile0;
+        int tl = live_tile(tile0 < 0 ? wave : tile0);
         if (tl >= ntile) return;
         int j = tl * 16 + l15;
         bool jin = j < N;
         long cofs = jin ? (long)xco(j) : 0;
         double cb[5], nb[5];
-        auto fetchc = [&](long co, int gi, double (&b)[5]) {          // gi: 0 or 1, resolved at compile time after unrolling
+        // ZK: a k-step reads its elements when any lane's lies outside the zero set of the tile it is fetched for (column key xkt),
+        // else X[0] (wave-uniform select of the offset), and in the MFMA block - straight-line code as before - every lane selects
+        // 0.0 for its elements of the set.  Lanes outside K carry ZP::xm_none, lanes outside N ZP::xk_none: in the set by definition.
+        int xk = 0, xk2 = 0;
+        if constexpr (ZK) xk = jin ? zp.xk(j) : ZP::xk_none;
+        auto fetchc = [&](long co, int gi, double (&b)[5], int xkt) {          // gi: 0 or 1, resolved at compile time after unrolling
 #pragma unroll
           for (int u = 0; u < 5; u++) {
-            const long o = (gi == 0 ? xr_[0][u] : xr_[NGC - 1][u]) + co;
+            long o = (gi == 0 ? xr_[0][u] : xr_[NGC - 1][u]) + co;
+            if constexpr (ZK) { if (__ballot(!zp.z(xkt, gi == 0 ? xm_[0][u] : xm_[NGC - 1][u])) == 0) o = 0; }
             b[u] = NTX ? __builtin_nontemporal_load(Xp + o) : Xp[o];
           }
         };
-        fetchc(cofs, 0, cb);
+        fetchc(cofs, 0, cb, xk);
         for (;;) {
           d4 acc[NTM];
 #pragma unroll
           for (int t = 0; t < NTM; t++) acc[t] = d4{0, 0, 0, 0};
-          const int tl2 = tl + tstride;
+          const int tl2 = live_tile(tl + tstride);                      // the prefetch below is for the next tile that is computed
           const int j2 = tl2 * 16 + l15;
           const bool jin2 = j2 < N;
           long cofs2 = 0;
 #pragma unroll
           for (int gi = 0; gi < NGC; gi++) {
             if (5 * gi >= nks) break;                                   // wave-uniform
-            if (gi + 1 < NGC && 5 * (gi + 1) < nks) fetchc(cofs, gi + 1, nb);
-            else if (tl2 < ntile) { cofs2 = jin2 ? (long)xco(j2) : 0; fetchc(cofs2, 0, nb); }
+            if (gi + 1 < NGC && 5 * (gi + 1) < nks) fetchc(cofs, gi + 1, nb, xk);
+            else if (tl2 < ntile) {
+              cofs2 = jin2 ? (long)xco(j2) : 0;
+              if constexpr (ZK) xk2 = jin2 ? zp.xk(j2) : ZP::xk_none;
+              fetchc(cofs2, 0, nb, xk2);
+            }
 #pragma unroll
             for (int u = 0; u < 5; u++) {
-              const bool kin = (kinm[gi] >> u) & 1u;
-              const double bv = (kin && jin) ? cb[u] : 0.0;
+              double bv;
+              if constexpr (ZK) bv = zp.z(xk, xm_[gi][u]) ? 0.0 : cb[u];
+              else {
+                const bool kin = (kinm[gi] >> u) & 1u;
+                bv = (kin && jin) ? cb[u] : 0.0;
+              }
 #pragma unroll
               for (int t = 0; t < NTM; t++) acc[t] = mfma(Sp[s_ro[t] + so_[gi][u]], bv, acc[t]);
             }
@@ -348,7 +416,7 @@ __device__ __attribute__((noinline)) void gemm_direct(int M, int N, int K, SP Sp
           }
           tl = tl2;
           if (tl >= ntile) break;
-          j = j2; jin = jin2; cofs = cofs2;
+          j = j2; jin = jin2; cofs = cofs2; xk = xk2;
         }
       };
       switch (ntm) {
