@@ -293,7 +293,11 @@ int mpbp_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* o
  *   method 1, global-state forward-backward: the S = prod_i q_i joint states of all nodes at one time (last node fastest),
  *     a_0 = g_0, a_{t+1} = g_{t+1} (a_t K_t), b_T = 1, b_t = K_t (g_{t+1} b_{t+1}) with g_t = prod phi^t prod psi^t and
  *     K_t(s -> s') = prod_i W_i^t(s'_i | s), every step normalised.  Exact on any graph at any T, cost T S^2.  Limits:
- *     S <= 2^16; not on chains periodic in time.  It delivers log Z, marginals and pair marginals only.
+ *     S <= 2^16; not on chains periodic in time.  It delivers log Z, marginals, same-time pair marginals and - by carrying
+ *     conditioned vectors v_t = a_t [s_i = x], v_{u+1} = g_{u+1} (v_u K_u) forward, many at once through an fp64 MFMA GEMM -
+ *     the two-time and alternate marginals below; never the joint.  The first such call keeps a_t and b_t of every t
+ *     (2 (T+1) S doubles); the vectors travel in batches of at most 512 rows (debug switch MPBP_EXACT_TT_ROWS=<n>, read at
+ *     each call; the results are bit-identical for every n).  MPBP_ENOMEM if either does not fit.
  * Refused at create with MPBP_EUNSUPPORTED: aliased graphs (InfiniteRegularGraph), q > 4, sizes over the limits.  All
  * sums run in a fixed order: two solves give bit-identical results.  Z = 0 (the observations exclude every trajectory)
  * is MPBP_EINVAL.
@@ -319,6 +323,15 @@ int mpbp_exact_site_marginals(mpbp_exact* x, int32_t node, double* out);
 /* the exact `pair_marginals(bp; p)` (src/exact.jl:85-100): the joint of the two trajectories of edge i -> j,
  * q_i^(T+1) q_j^(T+1) doubles, C-ordered [traj_i][traj_j] whichever of i, j is the larger */
 int mpbp_exact_edge_marginals(mpbp_exact* x, int32_t edge, double* out);
+/* Both methods.  Two-time marginals of the listed nodes in the layout and maxdist convention of mpbp_twovar_marginals:
+ * out[k][t][u][x + q*y] = p(x_{nodes[k]}^t = x, x_{nodes[k]}^u = y) for t < u <= t + maxdist (maxdist <= 0: all), zero
+ * elsewhere and on padding states; `out`: host, n_nodes (T+1)^2 q^2 doubles.  Method 0 (a loaded p included): strided
+ * reductions of p; method 1: conditioned vectors, each table divided by its own total, a state excluded by an observation
+ * gives a zero row.  A node out of range is MPBP_EINVAL. */
+int mpbp_exact_twovar_marginals(mpbp_exact* x, const int32_t* nodes, int32_t n_nodes, int32_t maxdist, double* out);
+/* Both methods.  `exact_alternate_marginals` (src/exact.jl:132-148) per directed edge e = (i -> j):
+ * out[x_i + q (x_j + q (t + T e))] = p(x_i^t, x_j^{t+1}) for t < T; `out`: host, q^2 T E doubles */
+int mpbp_exact_alternate_marginals(mpbp_exact* x, double* out);
 
 /*
  * Population dynamics for the equilibrium magnetisation of the Ising model on infinite diluted graphs (reference

@@ -234,6 +234,44 @@ function twovar_marginals_device(bp::MPBP, be::HIPBackend; sites=collect(vertice
 end
 
 """
+    exact_twovar_marginals(bp, be; method=1, sites, maxdist) -> Array{Float64,5}  # [x_t, x_u, u, t, k]
+    exact_alternate_marginals(bp, be; method=1) -> Array{Float64,4}               # [x_i^t, x_j^{t+1}, t, e]
+
+The exact counterparts of `twovar_marginals_device` and of `alternate_marginals` (src/mpbp.jl:270-280), from an exact
+solver made for the call (`mpbp_exact_twovar_marginals`, `mpbp_exact_alternate_marginals`): `method = 0` reduces the
+enumerated joint, `method = 1` carries conditioned vectors through the global-state transfer matrix and works at any T
+(`prod nstates <= 2^16`).  Same layout and `maxdist` convention as the belief form; padding states are zero.
+"""
+function exact_twovar_marginals(bp::MPBP, be::HIPBackend; method::Integer=1, sites=collect(vertices(bp.g)),
+                                maxdist::Integer=getT(bp) + 1)
+    L = getT(bp) + 1; q = be.q
+    out = zeros(Float64, q, q, L, L, length(sites))
+    with_exact(be, method) do x
+        check(ccall((:mpbp_exact_twovar_marginals, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Int32, Int32, Ptr{Float64}),
+                    x, Int32.(sites .- 1), length(sites), maxdist, out), be.h)
+    end
+    out
+end
+
+function exact_alternate_marginals(bp::MPBP, be::HIPBackend; method::Integer=1)
+    out = zeros(Float64, be.q, be.q, getT(bp), ne(bp.g))
+    with_exact(be, method) do x
+        check(ccall((:mpbp_exact_alternate_marginals, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), x, out), be.h)
+    end
+    out
+end
+
+function with_exact(f, be::HIPBackend, method::Integer)
+    x = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mpbp_exact_create, LIB), Cint, (Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Int32), x, be.h, method), be.h)
+    try
+        f(x[])
+    finally
+        ccall((:mpbp_exact_destroy, LIB), Cvoid, (Ptr{Cvoid},), x[])
+    end
+end
+
+"""
     allgather_slots!(be, comm, rank, world, slots_per_rank)
 
 Exchange step of the multi-GPU path: one in-place RCCL all-gather of the message slab and one of the bond table

@@ -13,7 +13,7 @@ from .mpbp import (CB_BP, MPBP, random_message, periodic_mpbp, periodic_mpbp_inf
                    alternate_marginals, alternate_correlations, expectation, logprob, reset, reset_observations,
                    is_free_dynamics)
 from .exact import (ExactSolver, exact_alternate_marginal_expectations, exact_alternate_marginals, exact_autocorrelations,
-                    exact_autocovariances, exact_marginal_expectations, exact_marginals, exact_pair_marginal_expectations,
+                    exact_autocovariances, exact_beliefs_tu, exact_marginal_expectations, exact_marginals, exact_pair_marginal_expectations,
                     exact_pair_marginals, exact_prob, site_marginals)
 from .equilibrium import (CB_Pop, Dirac, Discrete, ErdosRenyi, Normal, Poisson, PopDyn, RandomRegular,
                           equilibrium_magnetization, equilibrium_observables, iterate_fixedpoint)

@@ -61,6 +61,7 @@ EXPORTS = ["mpbp_create", "mpbp_destroy", "mpbp_last_error", "mpbp_slab_layout",
            "mpbp_sampler_pair_marginals", "mpbp_sampler_twovar_marginals", "mpbp_sampler_counts", "mpbp_philox4x32_10",
            "mpbp_exact_create", "mpbp_exact_destroy", "mpbp_exact_solve", "mpbp_exact_marginals", "mpbp_exact_pair_marginals",
            "mpbp_exact_prob", "mpbp_exact_set_prob", "mpbp_exact_site_marginals", "mpbp_exact_edge_marginals",
+           "mpbp_exact_twovar_marginals", "mpbp_exact_alternate_marginals",
            "mpbp_popdyn_create", "mpbp_popdyn_destroy", "mpbp_popdyn_set_distribution", "mpbp_popdyn_iterate",
            "mpbp_popdyn_get_population", "mpbp_popdyn_set_population", "mpbp_popdyn_magnetization"]
 
@@ -168,6 +169,8 @@ def lib():
     L.mpbp_exact_set_prob.argtypes = [C.c_void_p, dp]
     L.mpbp_exact_site_marginals.argtypes = [C.c_void_p, C.c_int32, dp]
     L.mpbp_exact_edge_marginals.argtypes = [C.c_void_p, C.c_int32, dp]
+    L.mpbp_exact_twovar_marginals.argtypes = [C.c_void_p, ip, C.c_int32, C.c_int32, dp]
+    L.mpbp_exact_alternate_marginals.argtypes = [C.c_void_p, dp]
     L.mpbp_popdyn_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_uint64, C.c_double, dp]
     L.mpbp_popdyn_destroy.argtypes = [C.c_void_p]
     L.mpbp_popdyn_destroy.restype = None

@@ -5,11 +5,13 @@
 //   1  forward-backward over the global state s of all nodes at one time (S = prod_i q_i states): exact on any graph at
 //      any T for S <= 2^16.  The transfer matrix K_t(s -> s') = prod_i W_i^t(s'_i | s) is never formed: the nodes are
 //      split in two halves, KA[s, s'_A] and KB[s, s'_B] are built once per time block, and a step is one fp64 GEMM.
+//      Two-time and alternate marginals carry many conditioned vectors through K at once (k_tt_step, fp64 MFMA).
 // Every sum runs in a fixed order that depends on the problem sizes only - workgroup partials over fixed-size chunks,
 // then one final pass - and there are no floating-point atomics: results do not depend on the launch geometry.
 #include "ctx.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <limits>
 
 namespace ex {
@@ -424,6 +426,160 @@ __global__ void __launch_bounds__(NT) k_tr_pair(const double* __restrict__ gamma
   }
 }
 
+// ------------------------------------------------------------------------------------------ method 1: conditioned vectors
+// Two-time and alternate marginals push R conditioned row vectors through K at once.  V and OUT are row-major [Rpad][S],
+// Rpad a multiple of 16 with the padding rows exactly 0.
+constexpr int TT_NRT = 8, TT_RB = 16 * TT_NRT;   // MFMA row tiles and rows of one row block
+constexpr int TT_LDV = KS + 1;                   // LDS row stride of the V tile: odd, so loader writes and MFMA operand reads spread over the banks
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+
+// OUT[r, (A', B')] = sum_s V[r, s] KA[s, A'] KB[s, B'] as an fp64 MFMA GEMM (M = Rpad, N = K = S).  A workgroup owns 64
+// columns and up to TT_RB rows: the tile KA (.) KB of a k-step is formed once in LDS and serves every row tile, so the MFMA
+// stream holds LDS reads and MFMAs only.  Each wave sums its 16 columns over s = 0, 1, ... in MFMA steps of 4: the order
+// depends on S alone, and a row never sees the rows that travel with it.
+__global__ void __launch_bounds__(NT) k_tt_step(const double* __restrict__ V, const double* __restrict__ KA,
+                                                const double* __restrict__ KB, int S, int SA, int SB, int Rpad,
+                                                double* __restrict__ OUT) {
+  __shared__ double sV[TT_RB][TT_LDV], sK[KS][TS];
+  const int n0 = blockIdx.x * TS, r0 = blockIdx.y * TT_RB;
+  const int nrt = min(TT_NRT, (Rpad - r0) / 16);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, l15 = lane & 15;
+  const int vk = threadIdx.x & 15, vr = threadIdx.x >> 4;     // loader of V: state s0 + vk of the rows r0 + 16 j + vr
+  const int kc = threadIdx.x & 63, kk0 = threadIdx.x >> 6;    // loader of K: column n0 + kc of the states s0 + kk0 + 4 j
+  const int n = n0 + kc;
+  const bool ncol = n < S;
+  const int cA = ncol ? n / SB : 0, cB = ncol ? n - cA * SB : 0;
+  d4 acc[TT_NRT];
+#pragma unroll
+  for (int j = 0; j < TT_NRT; j++) acc[j] = d4{0.0, 0.0, 0.0, 0.0};
+  double pv[TT_NRT], pa[KS / 4], pb[KS / 4];
+  auto fetch = [&](int s0) {
+#pragma unroll
+    for (int j = 0; j < TT_NRT; j++)
+      pv[j] = (j < nrt && s0 + vk < S) ? V[(size_t)(r0 + 16 * j + vr) * S + s0 + vk] : 0.0;
+#pragma unroll
+    for (int j = 0; j < KS / 4; j++) {
+      const int s = s0 + kk0 + 4 * j;
+      const bool ok = ncol && s < S;
+      pa[j] = ok ? KA[(size_t)s * SA + cA] : 0.0;
+      pb[j] = ok ? KB[(size_t)s * SB + cB] : 0.0;
+    }
+  };
+  fetch(0);
+  for (int s0 = 0; s0 < S; s0 += KS) {
+#pragma unroll
+    for (int j = 0; j < TT_NRT; j++) sV[16 * j + vr][vk] = pv[j];
+#pragma unroll
+    for (int j = 0; j < KS / 4; j++) sK[kk0 + 4 * j][kc] = pa[j] * pb[j];
+    __syncthreads();
+    if (s0 + KS < S) fetch(s0 + KS);        // the next tiles travel while this one is multiplied
+#pragma unroll
+    for (int k4 = 0; k4 < KS / 4; k4++) {
+      const double b = sK[4 * k4 + g][wave * 16 + l15];
+#pragma unroll
+      for (int j = 0; j < TT_NRT; j++)
+        if (j < nrt) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(sV[16 * j + l15][4 * k4 + g], b, acc[j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const int col = n0 + wave * 16 + l15;
+  if (col < S) {
+#pragma unroll
+    for (int j = 0; j < TT_NRT; j++)
+      if (j < nrt) {
+#pragma unroll
+        for (int v = 0; v < 4; v++) OUT[(size_t)(r0 + 16 * j + g + 4 * v) * S + col] = acc[j][v];   // C: row g + 4 v, column l15
+      }
+  }
+}
+
+__global__ void __launch_bounds__(NT) k_tt_fill(double* __restrict__ v, int S, double val) {
+  const int s = blockIdx.x * NT + threadIdx.x;
+  if (s < S) v[s] = val;
+}
+
+// admits an origin: the rows of member m (blockIdx.y) in the slot that starts at row `slot0` become a (.) [s_i = x]
+__global__ void __launch_bounds__(NT) k_tt_admit(const double* __restrict__ a, const Node* __restrict__ nodes,
+                                                 const int32_t* __restrict__ sstride, const int32_t* __restrict__ mem_row,
+                                                 const int32_t* __restrict__ mem_node, int slot0, int S, double* __restrict__ V) {
+  const int s = blockIdx.x * NT + threadIdx.x;
+  if (s >= S) return;
+  const int i = mem_node[blockIdx.y], qi = nodes[i].qi, xs = (s / sstride[i]) % qi;
+  const double w = a[s];
+  for (int x = 0; x < qi; x++) V[(size_t)(slot0 + mem_row[blockIdx.y] + x) * S + s] = x == xs ? w : 0.0;
+}
+
+// one workgroup per (member, slot): the q_i rows of the group are multiplied by g and divided by their common total
+// (fixed order; a group that is identically zero stays zero)
+__global__ void __launch_bounds__(NT) k_tt_scale(double* __restrict__ V, const double* __restrict__ gmul,
+                                                 const Node* __restrict__ nodes, const int32_t* __restrict__ mem_row,
+                                                 const int32_t* __restrict__ mem_node, int G, int S) {
+  __shared__ double red[NT];
+  const int qi = nodes[mem_node[blockIdx.x]].qi;
+  double* v = V + (size_t)(blockIdx.y * G + mem_row[blockIdx.x]) * S;
+  double a = 0.0;
+  for (int x = 0; x < qi; x++)
+    for (int s = threadIdx.x; s < S; s += NT) {
+      const double w = v[(size_t)x * S + s] * gmul[s];
+      v[(size_t)x * S + s] = w;
+      a += w;
+    }
+  red[threadIdx.x] = a;
+  tree_sum(red);
+  const double z = red[0];
+  if (!(z > 0.0)) return;
+  for (int x = 0; x < qi; x++)
+    for (int s = threadIdx.x; s < S; s += NT) v[(size_t)x * S + s] /= z;
+}
+
+// read-out after the step u -> u + 1: one workgroup per (read item, slot).  The slot holds the origin t, the latest one
+// admitted into it; if it is still alive (t > u - md), bins[x][y] = sum_s v_x(s) b(s) [s_j = y] over the q_i rows of the
+// item, divided by their total, go to out[base + t st_t + (u + 1) st_u + x + q y].  Padding entries stay as they are (0).
+__global__ void __launch_bounds__(NT) k_tt_read(const double* __restrict__ V, const double* __restrict__ b,
+                                                const Node* __restrict__ nodes, const int32_t* __restrict__ sstride,
+                                                const int32_t* __restrict__ rd_row, const int32_t* __restrict__ rd_src,
+                                                const int32_t* __restrict__ rd_dst, const int64_t* __restrict__ rd_base,
+                                                int G, int W, int t1, int t2, int u, int md, int64_t st_t, int64_t st_u,
+                                                int S, int q, double* __restrict__ out) {
+  __shared__ double red[NT];
+  __shared__ double bins[MAXQ * MAXQ];
+  const int w = blockIdx.y, it = blockIdx.x;
+  const int d = min(u, t2) - t1;
+  const int t = t1 + d - (((d - w) % W) + W) % W;
+  if (t < t1 || t + md <= u) return;
+  const int qi = nodes[rd_src[it]].qi, j = rd_dst[it], qj = nodes[j].qi, sj = sstride[j];
+  const double* v = V + (size_t)(w * G + rd_row[it]) * S;
+  double a[MAXQ * MAXQ];
+#pragma unroll
+  for (int k = 0; k < MAXQ * MAXQ; k++) a[k] = 0.0;
+  for (int s = threadIdx.x; s < S; s += NT) {
+    const double bw = b[s];
+    const int y = (s / sj) % qj;
+#pragma unroll
+    for (int x = 0; x < MAXQ; x++) {
+      const double val = x < qi ? v[(size_t)x * S + s] * bw : 0.0;
+#pragma unroll
+      for (int yy = 0; yy < MAXQ; yy++) a[x + MAXQ * yy] += yy == y ? val : 0.0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < MAXQ * MAXQ; k++) {
+    red[threadIdx.x] = a[k];
+    tree_sum(red);
+    if (threadIdx.x == 0) bins[k] = red[0];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int y = 0; y < qj; y++)
+      for (int x = 0; x < qi; x++) tot += bins[x + MAXQ * y];
+    double* o = out + rd_base[it] + (int64_t)t * st_t + (int64_t)(u + 1) * st_u;
+    for (int y = 0; y < qj; y++)
+      for (int x = 0; x < qi; x++) o[x + q * y] = tot > 0.0 ? bins[x + MAXQ * y] / tot : 0.0;
+  }
+}
+
 }  // namespace ex
 
 // ================================================================================================ host side
@@ -451,6 +607,11 @@ struct mpbp_exact {
   int32_t *d_sstride = nullptr, *d_col = nullptr;
   double *d_g = nullptr, *d_a = nullptr, *d_b = nullptr, *d_H = nullptr, *d_KA = nullptr, *d_KB = nullptr, *d_tpart = nullptr,
          *d_z = nullptr;
+  // conditioned vectors (two-time and alternate marginals): a_t and b_t of every t, kept from the first such call on
+  double *d_aa = nullptr, *d_bb = nullptr;
+  double* d_V[2] = {nullptr, nullptr}; size_t V_cap[2] = {0, 0};
+  int32_t *d_mem_row = nullptr, *d_mem_node = nullptr, *d_rd_row = nullptr, *d_rd_src = nullptr, *d_rd_dst = nullptr;
+  int64_t* d_rd_base = nullptr;
   double logZ = std::numeric_limits<double>::quiet_NaN();
 
   int fail(int code, const char* fmt, ...) {
@@ -592,7 +753,9 @@ extern "C" void mpbp_exact_destroy(mpbp_exact* x) {
                   (void*)x->d_edst, (void*)x->d_logphi, (void*)x->d_hlpsi, (void*)x->d_p, (void*)x->d_pmax, (void*)x->d_psum,
                   (void*)x->d_res, (void*)x->d_part, (void*)x->d_site, (void*)x->d_edge, (void*)x->d_out, (void*)x->d_sstride,
                   (void*)x->d_col, (void*)x->d_g, (void*)x->d_a, (void*)x->d_b, (void*)x->d_H, (void*)x->d_KA, (void*)x->d_KB,
-                  (void*)x->d_tpart, (void*)x->d_z})
+                  (void*)x->d_tpart, (void*)x->d_z, (void*)x->d_aa, (void*)x->d_bb, (void*)x->d_V[0], (void*)x->d_V[1],
+                  (void*)x->d_mem_row, (void*)x->d_mem_node, (void*)x->d_rd_row, (void*)x->d_rd_src, (void*)x->d_rd_dst,
+                  (void*)x->d_rd_base})
     if (p) hipFree(p);
   delete x;
 }
@@ -889,6 +1052,11 @@ static int tr_solve(mpbp_exact* x) {
     lz += std::log(z[t]);
   }
   x->logZ = lz;
+  if (x->d_aa) XCHK(x, hipMemcpyAsync(x->d_aa, x->d_a, sizeof(double) * (size_t)L * S, hipMemcpyDeviceToDevice, st));
+  if (x->d_bb) {
+    hipLaunchKernelGGL(ex::k_tt_fill, dim3(gS), dim3(ex::NT), 0, st, x->d_bb + (size_t)T * S, S, 1.0);
+    XCHK(x, hipGetLastError());
+  }
   // backward: b_T = 1, b_t = K_t (g_{t+1} b_{t+1}), each rescaled; a_t is overwritten by gamma_t = a_t b_t
   XCHK(x, hipMemcpyAsync(x->d_H, x->d_g + (size_t)T * S, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
   for (int t = T - 1; t >= 0; t--) {
@@ -901,6 +1069,7 @@ static int tr_solve(mpbp_exact* x) {
     hipLaunchKernelGGL(ex::k_scale, dim3(1), dim3(ex::NT), 0, st, x->d_b, S, (double*)nullptr, x->d_g + (size_t)t * S, x->d_H,
                        x->d_a + (size_t)t * S);
     XCHK(x, hipGetLastError());
+    if (x->d_bb) XCHK(x, hipMemcpyAsync(x->d_bb + (size_t)t * S, x->d_b, sizeof(double) * S, hipMemcpyDeviceToDevice, st));
   }
   XCHK(x, hipStreamSynchronize(st));
   x->solved = true;
@@ -1022,6 +1191,195 @@ extern "C" int mpbp_exact_edge_marginals(mpbp_exact* x, int32_t edge, double* ou
   // out[traj_i][traj_j] whichever of the two comes first in p
   if ((rc = enum_edge(x, lo, hi, x->d_edge, i == lo ? (int64_t)x->Qn[hi] : 1, i == lo ? 1 : (int64_t)x->Qn[lo]))) return rc;
   XCHK(x, hipMemcpyAsync(out, x->d_edge, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  XCHK(x, hipStreamSynchronize(c->stream));
+  return MPBP_OK;
+}
+
+// ------------------------------------------------------------------------------------------ conditioned vectors, host
+// Two-time marginals p(x_i^t, x_i^u) and alternate marginals p(x_i^t, x_j^{t+1}) at any T.  An origin (t, i, x) is the row
+// vector v_t = a_t (.) [s_i = x]; it is carried forward by v_{u+1} = g_{u+1} (.) (v_u K_u) and read against b_u, at node i
+// itself (two-time) or at the neighbours one step later (alternate).  The q_i rows of one (t, i) form a group that is
+// rescaled by its common total, so every table keeps its proportions.  The rows live in W slots of G rows, one slot per
+// live origin time; the members (nodes) and origin times are cut into passes whose W G rows respect the row cap.  No row
+// sees its companions, so the cut does not change a bit of the result.
+static int tt_ready(mpbp_exact* x) {
+  hipSetDevice(x->ctx->device);
+  int rc = ex_refresh(x);
+  if (rc) return rc;
+  if (!x->d_aa || !x->d_bb) {
+    const size_t bytes = sizeof(double) * (size_t)x->ctx->L * x->S;
+    size_t fre = 0, tot = 0;
+    XCHK(x, hipMemGetInfo(&fre, &tot));
+    if (2 * bytes + (size_t(64) << 20) > fre)
+      return x->fail(MPBP_ENOMEM, "exact solver: a_t and b_t of every time (%zu MiB) do not fit the %zu MiB of free device memory", (2 * bytes) >> 20, fre >> 20);
+    if (!x->d_aa) XCHK(x, hipMalloc((void**)&x->d_aa, bytes));
+    if (!x->d_bb) XCHK(x, hipMalloc((void**)&x->d_bb, bytes));
+    x->solved = false;           // the next solve keeps them (same arithmetic, same log Z)
+  }
+  if (x->solved) return MPBP_OK;
+  return tr_solve(x);
+}
+
+static int tt_row_cap() {
+  const char* e = std::getenv("MPBP_EXACT_TT_ROWS");
+  long v = e ? std::atol(e) : 0;
+  if (v <= 0) v = 512;
+  return (int)std::min<long>(std::max<long>(v, ex::MAXQ), 1 << 20);
+}
+
+struct TTRead { int32_t src, dst; int64_t base; };   // rows of member `src`, read at node `dst`, written from out + base
+
+// one pass: the members mem[m0, m1) with their read items, origins t1 .. t2, lifetime md, W slots
+static int tt_pass(mpbp_exact* x, const std::vector<int32_t>& mem_node, const std::vector<std::vector<TTRead>>& reads, int m0, int m1,
+                   int t1, int t2, int md, int W, int64_t st_t, int64_t st_u, double* d_out) {
+  mpbp_ctx* c = x->ctx;
+  const int T = c->T, S = x->S, q = c->q;
+  hipStream_t st = c->stream;
+  std::vector<int32_t> mrow, mnode, rrow, rsrc, rdst;
+  std::vector<int64_t> rbase;
+  int G = 0;
+  for (int m = m0; m < m1; m++) {
+    mrow.push_back(G); mnode.push_back(mem_node[m]);
+    for (const TTRead& r : reads[m]) { rrow.push_back(G); rsrc.push_back(r.src); rdst.push_back(r.dst); rbase.push_back(r.base); }
+    G += c->qnode[mem_node[m]];
+  }
+  const int nmem = m1 - m0, nrd = (int)rrow.size();
+  if (nrd == 0) return MPBP_OK;
+  const int Rpad = (W * G + 15) / 16 * 16;
+  const size_t nV = (size_t)Rpad * S;
+  if (x->V_cap[0] < nV || x->V_cap[1] < nV) {
+    size_t fre = 0, tot = 0;
+    XCHK(x, hipMemGetInfo(&fre, &tot));
+    if (2 * nV * sizeof(double) + (size_t(64) << 20) > fre + (x->V_cap[0] + x->V_cap[1]) * sizeof(double))
+      return x->fail(MPBP_ENOMEM, "exact solver: a batch of %d conditioned vectors (2 x %zu MiB) does not fit the %zu MiB of free device memory; lower MPBP_EXACT_TT_ROWS", Rpad, (nV * sizeof(double)) >> 20, fre >> 20);
+  }
+  for (int k = 0; k < 2; k++) {
+    XCHK(x, ex_reserve(x->d_V[k], x->V_cap[k], nV));
+    XCHK(x, hipMemsetAsync(x->d_V[k], 0, sizeof(double) * nV, st));
+  }
+  XCHK(x, ex_upload(x->d_mem_row, mrow, st));
+  XCHK(x, ex_upload(x->d_mem_node, mnode, st));
+  XCHK(x, ex_upload(x->d_rd_row, rrow, st));
+  XCHK(x, ex_upload(x->d_rd_src, rsrc, st));
+  XCHK(x, ex_upload(x->d_rd_dst, rdst, st));
+  XCHK(x, ex_upload(x->d_rd_base, rbase, st));
+  const unsigned gS = (unsigned)((S + ex::NT - 1) / ex::NT);
+  int cur = 0, rc;
+  const int ulast = std::min(T - 1, t2 + md - 1);
+  for (int u = t1; u <= ulast; u++) {
+    if (!x->one_block && (rc = tr_kron(x, u))) return rc;
+    if (u <= t2) {
+      hipLaunchKernelGGL(ex::k_tt_admit, dim3(gS, nmem), dim3(ex::NT), 0, st, x->d_aa + (size_t)u * S, x->d_nodes, x->d_sstride,
+                         x->d_mem_row, x->d_mem_node, ((u - t1) % W) * G, S, x->d_V[cur]);
+      XCHK(x, hipGetLastError());
+    }
+    hipLaunchKernelGGL(ex::k_tt_step, dim3((S + ex::TS - 1) / ex::TS, (Rpad + ex::TT_RB - 1) / ex::TT_RB), dim3(ex::NT), 0, st, x->d_V[cur],
+                       x->d_KA, x->d_KB, S, x->SA, x->SB, Rpad, x->d_V[cur ^ 1]);
+    XCHK(x, hipGetLastError());
+    cur ^= 1;
+    hipLaunchKernelGGL(ex::k_tt_scale, dim3(nmem, W), dim3(ex::NT), 0, st, x->d_V[cur], x->d_g + (size_t)(u + 1) * S, x->d_nodes,
+                       x->d_mem_row, x->d_mem_node, G, S);
+    XCHK(x, hipGetLastError());
+    hipLaunchKernelGGL(ex::k_tt_read, dim3(nrd, W), dim3(ex::NT), 0, st, x->d_V[cur], x->d_bb + (size_t)(u + 1) * S, x->d_nodes,
+                       x->d_sstride, x->d_rd_row, x->d_rd_src, x->d_rd_dst, x->d_rd_base, G, W, t1, t2, u, md, st_t, st_u, S, q, d_out);
+    XCHK(x, hipGetLastError());
+  }
+  return MPBP_OK;
+}
+
+// all passes of one call: members are cut where a slot would exceed the row cap, origin times where the live slots would
+static int tt_run(mpbp_exact* x, const std::vector<int32_t>& mem_node, const std::vector<std::vector<TTRead>>& reads, int md,
+                  int64_t st_t, int64_t st_u, double* d_out) {
+  mpbp_ctx* c = x->ctx;
+  const int T = c->T, cap = tt_row_cap(), nm = (int)mem_node.size();
+  int rc;
+  if (x->one_block && (rc = tr_kron(x, 0))) return rc;
+  const int life = std::min(md, T);
+  for (int m0 = 0; m0 < nm;) {
+    int m1 = m0, G = 0;
+    while (m1 < nm && (m1 == m0 || G + c->qnode[mem_node[m1]] <= cap)) G += c->qnode[mem_node[m1++]];
+    const int W = std::min(life, std::max(1, cap / G));
+    if (W == life) {
+      if ((rc = tt_pass(x, mem_node, reads, m0, m1, 0, T - 1, md, W, st_t, st_u, d_out))) return rc;
+    } else {
+      for (int t1 = 0; t1 < T; t1 += W)
+        if ((rc = tt_pass(x, mem_node, reads, m0, m1, t1, std::min(T - 1, t1 + W - 1), md, W, st_t, st_u, d_out))) return rc;
+    }
+    m0 = m1;
+  }
+  return MPBP_OK;
+}
+
+extern "C" int mpbp_exact_twovar_marginals(mpbp_exact* x, const int32_t* nodes, int32_t n_nodes, int32_t maxdist, double* out) {
+  if (!x || !out || n_nodes < 0 || (n_nodes > 0 && !nodes)) return MPBP_EINVAL;
+  mpbp_ctx* c = x->ctx;
+  const int N = c->N, L = c->L, T = c->T, q = c->q;
+  for (int k = 0; k < n_nodes; k++)
+    if (nodes[k] < 0 || nodes[k] >= N) return x->fail(MPBP_EINVAL, "mpbp_exact_twovar_marginals: node %d out of range", nodes[k]);
+  const size_t n = (size_t)n_nodes * L * L * q * q;
+  if (n == 0) return MPBP_OK;
+  const int md = maxdist <= 0 ? std::max(T, 1) : std::min<int>(maxdist, std::max(T, 1));
+  int rc;
+  if ((rc = x->method == 0 ? enum_ready(x) : tt_ready(x))) return rc;
+  XCHK(x, ex_reserve(x->d_out, x->out_cap, n));
+  XCHK(x, hipMemsetAsync(x->d_out, 0, sizeof(double) * n, c->stream));
+  const int64_t blk = (int64_t)q * q;
+  if (x->method == 0) {
+    // p viewed as [before, x_i^t, between, x_i^u, after]: one strided reduction per (k, t, u)
+    for (int k = 0; k < n_nodes; k++) {
+      const int i = nodes[k];
+      const uint64_t qi = (uint64_t)c->qnode[i], pre = prod_range(x->Qn, 0, i), post = prod_range(x->Qn, i + 1, N);
+      for (int t = 0; t < L; t++)
+        for (int u = t + 1; u < L && u <= t + md; u++)
+          if ((rc = reduce5(x, x->d_p, pre * ipow(qi, t), qi, ipow(qi, u - t - 1), qi, ipow(qi, L - 1 - u) * post,
+                            x->d_out + (((int64_t)k * L + t) * L + u) * blk, 1, q))) return rc;
+    }
+  } else if (T > 0) {
+    std::vector<int32_t> mem(nodes, nodes + n_nodes);
+    std::vector<std::vector<TTRead>> reads(n_nodes);
+    for (int k = 0; k < n_nodes; k++) reads[k].push_back(TTRead{nodes[k], nodes[k], (int64_t)k * L * L * blk});
+    if ((rc = tt_run(x, mem, reads, md, (int64_t)L * blk, blk, x->d_out))) return rc;
+  }
+  XCHK(x, hipMemcpyAsync(out, x->d_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  XCHK(x, hipStreamSynchronize(c->stream));
+  return MPBP_OK;
+}
+
+extern "C" int mpbp_exact_alternate_marginals(mpbp_exact* x, double* out) {
+  if (!x || !out) return MPBP_EINVAL;
+  mpbp_ctx* c = x->ctx;
+  const int N = c->N, L = c->L, T = c->T, E = c->E, q = c->q;
+  const size_t n = (size_t)q * q * T * E;
+  if (n == 0) return MPBP_OK;
+  int rc;
+  if ((rc = x->method == 0 ? enum_ready(x) : tt_ready(x))) return rc;
+  XCHK(x, ex_reserve(x->d_out, x->out_cap, n));
+  XCHK(x, hipMemsetAsync(x->d_out, 0, sizeof(double) * n, c->stream));
+  const int64_t blk = (int64_t)q * q;
+  if (x->method == 0) {
+    // p viewed as [before, first kept digit, between, second kept digit, after]; the kept digits are (i, t) and (j, t + 1)
+    for (int e = 0; e < E; e++) {
+      const int i = c->edge_src[e], j = c->edge_dst[e], lo = std::min(i, j), hi = std::max(i, j);
+      const uint64_t ql = (uint64_t)c->qnode[lo], qh = (uint64_t)c->qnode[hi];
+      const uint64_t pre = prod_range(x->Qn, 0, lo), mid = prod_range(x->Qn, lo + 1, hi), post = prod_range(x->Qn, hi + 1, N);
+      for (int t = 0; t < T; t++) {
+        const int tl = i == lo ? t : t + 1, th = i == lo ? t + 1 : t;      // times kept at the lower and at the higher node
+        if ((rc = reduce5(x, x->d_p, pre * ipow(ql, tl), ql, ipow(ql, L - 1 - tl) * mid * ipow(qh, th), qh, ipow(qh, L - 1 - th) * post,
+                          x->d_out + ((int64_t)e * T + t) * blk, i == lo ? 1 : q, i == lo ? q : 1))) return rc;
+      }
+    }
+  } else {
+    std::vector<int32_t> mem;
+    std::vector<std::vector<TTRead>> reads;
+    for (int i = 0; i < N; i++) {
+      std::vector<TTRead> r;
+      for (int e = 0; e < E; e++)
+        if (c->edge_src[e] == i) r.push_back(TTRead{i, c->edge_dst[e], (int64_t)e * T * blk});
+      if (!r.empty()) { mem.push_back(i); reads.push_back(r); }
+    }
+    if ((rc = tt_run(x, mem, reads, 1, blk, 0, x->d_out))) return rc;
+  }
+  XCHK(x, hipMemcpyAsync(out, x->d_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
   XCHK(x, hipStreamSynchronize(c->stream));
   return MPBP_OK;
 }

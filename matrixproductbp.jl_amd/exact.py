@@ -4,7 +4,10 @@ MPBP run is compared against.
 Two methods.  `"enumerate"` is the reference's: the probability of every one of the Q = prod_i q_i^(T+1) trajectories
 (Q <= 2^32), from which every `exact_*` quantity follows.  `"transfer"` is a forward-backward recursion over the joint
 state of all nodes at one time (S = prod_i q_i <= 2^16 states): exact on any graph, loopy or not, at ANY T - it gives
-log Z, marginals and same-time pair marginals, not the joint.  `"auto"` enumerates when Q <= 2^26, else transfers.
+log Z, marginals, same-time pair marginals and, through `ExactSolver.twovar_marginals` / `.alternate_twovar_marginals`, the
+two-time and alternate marginals; not the joint.  `"auto"` enumerates when Q <= 2^26, else transfers.  The module functions
+for two-time quantities (`exact_beliefs_tu`, `exact_autocorrelations`, `exact_autocovariances`, `exact_alternate_marginals`)
+enumerate wherever that is possible and go to a transfer solver only where enumeration is refused for size.
 
 Layout of `p`: a C-ordered array of shape `[q_0]*(T+1) + [q_1]*(T+1) + ...` (node-major, time inside), 0-based states.
 Functions `f` receive 1-based states, as everywhere in this package.  The reference's bare `pair_marginals(bp; p)` is
@@ -18,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import MPBPError
-from .mpbp import MPBP, _dp
+from .mpbp import MPBP, _abi_maxdist, _dp, _ip
 
 ENUM_AUTO_MAX = 1 << 26       # "auto" enumerates up to this many configurations
 ENUM_MAX = 1 << 32
@@ -159,7 +162,8 @@ class ExactSolver:
         return self._cache["edge"]
 
     def alternate_marginals(self):
-        """`exact_alternate_marginals` (src/exact.jl:132-148): `out[e][t][x_i^t, x_j^{t+1}]`, t < T"""
+        """`exact_alternate_marginals` (src/exact.jl:132-148): `out[e][t][x_i^t, x_j^{t+1}]`, t < T, as axis sums of
+        `edge_marginals()` (enumeration only).  The form for both methods, at any T: `alternate_twovar_marginals()`."""
         if "alt" not in self._cache:
             L = self.bp.T + 1
             out = []
@@ -169,7 +173,9 @@ class ExactSolver:
         return self._cache["alt"]
 
     def autocorrelations(self, f=None):
-        """`exact_autocorrelations(f, bp)` (src/exact.jl:161-186): `out[i][t, u]` = E[f(x_i^t, i) f(x_i^u, i)], t < u"""
+        """`exact_autocorrelations(f, bp)` (src/exact.jl:161-186): `out[i][t, u]` = E[f(x_i^t, i) f(x_i^u, i)], t < u, from
+        `site_marginals()` (enumeration only).  The form for both methods, at any T: `twovar_autocorrelations(f)`, built
+        on `twovar_marginals()`."""
         f = (lambda x, i: x) if f is None else f
         L = self.bp.T + 1
         out = []
@@ -182,6 +188,53 @@ class ExactSolver:
                     r[t, u] = fx @ p @ fx
             out.append(r)
         return out
+
+    # --- two-time quantities on both methods (mpbp_exact_twovar_marginals / mpbp_exact_alternate_marginals) -----------
+    def _twovar_raw(self, sites, maxdist):
+        bp = self.bp
+        L, q = bp.T + 1, bp.q
+        nodes = np.ascontiguousarray(sites, dtype=np.int32)
+        buf = np.zeros(len(sites) * L * L * q * q)
+        md = _abi_maxdist(maxdist)
+        if md >= 0 and len(sites) > 0:       # maxdist = 0: no pair at all, no library call (the ABI's 0 means "all")
+            self._check(self._L.mpbp_exact_twovar_marginals(self._h, _ip(nodes), int(nodes.size), md, _dp(buf)))
+        return buf.reshape((len(sites), L, L, q, q))           # [k][t][u][y][x]
+
+    def twovar_marginals(self, sites=None, maxdist=None):
+        """Exact two-time marginals in the shape of `beliefs_tu`: `out[k][t][u][x_t, x_u]`, a q_i x q_i array for
+        t < u <= t + maxdist and None elsewhere, for the listed nodes (all by default).  Enumeration: strided reductions
+        of p; transfer: conditioned vectors carried through the transfer matrix, at any T.  Nothing is cached."""
+        bp = self.bp
+        sites = list(range(bp.g.nv())) if sites is None else [int(i) for i in sites]
+        L = bp.T + 1
+        arr = self._twovar_raw(sites, maxdist)
+        md = L if maxdist is None else int(maxdist)
+        qs = [int(bp.qnode[i]) if 0 <= i < bp.g.nv() else bp.q for i in sites]
+        return [[[arr[k, t, u, :qs[k], :qs[k]].T.copy() if t < u <= t + md else None for u in range(L)] for t in range(L)]
+                for k in range(len(sites))]
+
+    def twovar_autocorrelations(self, f=None, sites=None, maxdist=None):
+        """`out[k][t, u]` = E[f(x_i^t, i) f(x_i^u, i)] for t < u <= t + maxdist (0 elsewhere), from `twovar_marginals`"""
+        f = (lambda x, i: x) if f is None else f
+        bp = self.bp
+        sites = list(range(bp.g.nv())) if sites is None else [int(i) for i in sites]
+        arr = self._twovar_raw(sites, maxdist)
+        out = []
+        for k, i in enumerate(sites):
+            fx = np.array([f(x + 1, i) if x < bp.qnode[i] else 0.0 for x in range(bp.q)], dtype=float)
+            out.append(np.einsum("tuyx,x,y->tu", arr[k], fx, fx))
+        return out
+
+    def alternate_twovar_marginals(self):
+        """`out[e][t][x_i^t, x_j^{t+1}]`, t < T, per directed edge e = (i -> j), on both methods and at any T"""
+        bp = self.bp
+        E, T, q = bp.g.ne(), bp.T, bp.q
+        buf = np.zeros(q * q * T * E)
+        if buf.size:
+            self._check(self._L.mpbp_exact_alternate_marginals(self._h, _dp(buf)))
+        m = buf.reshape((q, q, T, E), order="F")
+        ends = bp._ends
+        return [[m[:bp.qnode[ends[e][0]], :bp.qnode[ends[e][1]], t, e].copy() for t in range(T)] for e in range(E)]
 
 
 def _solver(bp, p_exact, method):
@@ -213,23 +266,51 @@ def exact_pair_marginals(bp: MPBP, p_exact=None):
     return _solver(bp, p_exact, "auto").pair_marginals()
 
 
+def _twotime_solver(bp, p_exact):
+    """The solver behind the two-time module functions: today's route, enumeration, wherever it works; a transfer solver
+    only where enumeration is refused for size (MPBPError -4).  A solver that is passed in is used as it is."""
+    if p_exact is not None:
+        return _solver(bp, p_exact, "enumerate")
+    try:
+        return ExactSolver(bp, "enumerate")
+    except MPBPError as e:
+        if e.code != -4:
+            raise
+        return ExactSolver(bp, "transfer")
+
+
+def exact_beliefs_tu(bp: MPBP, sites=None, maxdist=None, p_exact=None):
+    """The exact counterpart of `beliefs_tu`: `out[k][t][u][x_t, x_u]` for t < u <= t + maxdist, None elsewhere"""
+    return _twotime_solver(bp, p_exact).twovar_marginals(sites, maxdist)
+
+
 def exact_alternate_marginals(bp: MPBP, p_exact=None):
     """src/exact.jl:132-148: `out[e][t][x_i^t, x_j^{t+1}]`"""
-    return _solver(bp, p_exact, "enumerate").alternate_marginals()
+    s = _twotime_solver(bp, p_exact)
+    return s.alternate_marginals() if s.method == "enumerate" else s.alternate_twovar_marginals()
 
 
-def exact_autocorrelations(*args, p_exact=None):
-    """`exact_autocorrelations(f, bp)` or `exact_autocorrelations(bp)` with f(x, i) = x (src/exact.jl:161-188)"""
+def exact_autocorrelations(*args, p_exact=None, maxdist=None):
+    """`exact_autocorrelations(f, bp)` or `exact_autocorrelations(bp)` with f(x, i) = x (src/exact.jl:161-188); with
+    `maxdist`, entries beyond t + maxdist are 0 as in `autocorrelations`"""
     f, bp = _f_bp(args)
-    return _solver(bp, p_exact, "enumerate").autocorrelations(f)
+    s = _twotime_solver(bp, p_exact)
+    if s.method != "enumerate":
+        return s.twovar_autocorrelations(f, maxdist=maxdist)
+    r = s.autocorrelations(f)
+    if maxdist is not None:
+        L = bp.T + 1
+        keep = np.array([[t < u <= t + int(maxdist) for u in range(L)] for t in range(L)])
+        r = [np.where(keep, ri, 0.0) for ri in r]
+    return r
 
 
-def exact_autocovariances(*args, r=None, mu=None, p_exact=None):
+def exact_autocovariances(*args, r=None, mu=None, p_exact=None, maxdist=None):
     """src/exact.jl:191-198: `covariance(r, mu) = r - mu mu'` (src/mpbp.jl:288)"""
     f, bp = _f_bp(args)
     if r is None or mu is None:
-        p_exact = _solver(bp, p_exact, "enumerate")
-    r = exact_autocorrelations(f, bp, p_exact=p_exact) if r is None else r
+        p_exact = _twotime_solver(bp, p_exact)
+    r = exact_autocorrelations(f, bp, p_exact=p_exact, maxdist=maxdist) if r is None else r
     mu = exact_marginal_expectations(f, bp, p_exact=p_exact) if mu is None else mu
     return [ri - np.outer(mi, mi) for ri, mi in zip(r, mu)]
 
@@ -266,6 +347,6 @@ def exact_pair_marginal_expectations(*args, m_exact=None, p_exact=None):
 
 
 def exact_alternate_marginal_expectations(*args, m_exact=None, p_exact=None):
-    """src/exact.jl:150-158: `out[e][t]` = E[f(x_i^t, e) f(x_j^{t+1}, e)]"""
+    """src/exact.jl:150-158: `out[e][t]` = E[f(x_i^t, e) f(x_j^{t+1}, e)] (at any T where enumeration is refused for size)"""
     f, bp = _f_bp(args)
     return _expectations(f, bp, exact_alternate_marginals(bp, p_exact) if m_exact is None else m_exact)
